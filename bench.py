@@ -15,17 +15,27 @@ gathered to rank 0 over RCCL (the job's only exchange).  7z is outside the path,
 reference's own timing split.  `--contexts C` runs C library contexts per GPU, each driven by its
 own host thread, so one pair's host round trips overlap another pair's kernels.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 Printed (rank 0): one JSON line.  value = the genome's target bases / max-over-ranks step time
-(strong scaling: the job is fixed, N GPUs share it); roofline of the dominant kernel (HIP events
-on the launching streams, SURVEY §8(d) algorithmic bytes) and of the whole job (DESIGN.md §4's
-design model beside SURVEY §8(d)'s); the reference compression.cpp timed on this host on
-BASELINE configs[0] (the chr21 pair); the chr1 record stream reconstructed on the GPU
-(configs[3]); the T2T-like genome (configs[4]'s shape, 24 pairs at UCSC lengths); the whole
-genome from FASTA files to record files (with and without the 7z step); per-chromosome sha256
-checked against the reference's, pinned in tests/golden/genome_manifest.json.
+(strong scaling: the job is fixed, N GPUs share it); ms_per_step = one timed step; the whole job's
+roofline (DESIGN.md §4's design model beside SURVEY §8(d)'s, from the steps' own statistics).  A
+plain run does no more than that: inputs, warm-up, the K timed steps, the line.
+
+--dump-outputs DIR writes what the last timed step computed -- every chromosome's record stream,
+the bytes a caller of the step receives -- as .npy files (dump_outputs below).  The inputs are
+seeded by the chromosome index, so two builds run with the same arguments are compared output for
+output.
+
+--full adds every other measurement and check to the line: the roofline of the dominant kernel
+(HIP events on the launching streams inside the timed region, SURVEY §8(d) algorithmic bytes) and
+the per-kernel table; the per-pair standalone costs; the reference compression.cpp timed on this
+host on BASELINE configs[0] (the chr21 pair); the chr1 record stream reconstructed on the GPU
+(configs[3]); chr1 at k = 21 (configs[1]); the T2T-like genome (configs[4]'s shape, 24 pairs at
+UCSC lengths); the whole genome from FASTA files to record files (with and without the 7z step);
+per-chromosome sha256 checked against the reference's, pinned in
+tests/golden/genome_manifest.json.  The --no-* options drop single legs of a --full run.
 
 The distributed pieces (timed_region, gather_streams, job_totals, check_pins) take the process
 group from torch.distributed and are exercised with gloo on CPU by tests/test_bench_cpu.py.
@@ -199,15 +209,57 @@ def check_pins(streams: dict | None, pins: dict) -> dict | None:
             "reference": "oracle/_ref (compression.cpp compiled unchanged), tests/golden/genome_manifest.json"}
 
 
+DUMP_SAMPLE_ELEMS = 10_000_000   # float32 samples over all streams: 40 MB of the 64 MB a dump may take
+DUMP_BLOCK = 4096
+
+
+def dump_outputs(streams: dict, out_dir: str) -> dict:
+    """The step's outputs as .npy files: for every chromosome <name>
+      <name>.npy         float32, the record stream's bytes -- all of them while every stream
+                         together fits DUMP_SAMPLE_ELEMS, else a sample of the stream at sorted
+                         positions drawn once from a generator seeded by the name and the length (so
+                         the same stream is sampled at the same positions in every run and build);
+      <name>_blocks.npy  float64 [blocks, 2], over every byte of the stream: per 4 KiB block the sum
+                         of its bytes and the sum of byte x (offset in the block + 1), both exact in
+                         float64 -- a difference outside the sample still shows;
+    and lengths.npy, float64, the streams' lengths in the order of their sorted names."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(streams)
+    total = sum(len(streams[n]) for n in names)
+    weights = np.arange(1, DUMP_BLOCK + 1, dtype=np.float64)
+    written = 0
+    for n in names:
+        b = np.frombuffer(streams[n], dtype=np.uint8)
+        if total <= DUMP_SAMPLE_ELEMS:
+            sample = b.astype(np.float32)
+        else:
+            k = max(1, len(b) * DUMP_SAMPLE_ELEMS // total) if len(b) else 0
+            rng = np.random.default_rng([zlib.crc32(n.encode()), len(b)])
+            sample = b[np.sort(rng.choice(len(b), size=k, replace=False))].astype(np.float32)
+        padded = np.zeros(-(-len(b) // DUMP_BLOCK) * DUMP_BLOCK, dtype=np.float64)
+        padded[:len(b)] = b
+        padded = padded.reshape(-1, DUMP_BLOCK)
+        blocks = np.stack([padded.sum(axis=1), padded @ weights], axis=1)
+        np.save(os.path.join(out_dir, n + ".npy"), sample)
+        np.save(os.path.join(out_dir, n + "_blocks.npy"), blocks)
+        written += sample.nbytes + blocks.nbytes
+    lengths = np.array([len(streams[n]) for n in names], dtype=np.float64)
+    np.save(os.path.join(out_dir, "lengths.npy"), lengths)
+    return {"dir": out_dir, "streams": len(names), "bytes": written + lengths.nbytes,
+            "sampled": total > DUMP_SAMPLE_ELEMS}
+
+
 def cpu_baseline_pointer() -> dict | None:
-    """N > 1 lines: the CPU baseline is measured by the N = 1 run only (rank 0, bounded sample);
-    repeat its committed value with a pointer to it."""
+    """Plain and N > 1 lines: the CPU baseline is measured by the N = 1 --full run only (rank 0,
+    bounded sample); repeat its committed value with a pointer to it."""
     try:
         doc = json.load(open(CPU_BASELINE_N1))
     except Exception:
         return None
     out = dict(doc)
-    out["measured_in"] = os.path.relpath(CPU_BASELINE_N1, REPO) + " (the N = 1 bench line; not re-run at N > 1)"
+    out["measured_in"] = os.path.relpath(CPU_BASELINE_N1, REPO) + " (the N = 1 --full bench line; not re-run here)"
     return out
 
 
@@ -668,7 +720,16 @@ def main() -> None:
     ap.add_argument("--no-k21", action="store_true", help="skip the configs[1] leg (chr1 at k = 21)")
     ap.add_argument("--only-steps", action="store_true",
                     help="the timed steps and the line only (traces): no per-pair costs, decompress, k=21, e2e, T2T")
+    ap.add_argument("--full", action="store_true",
+                    help="every other measurement and check beside the timed steps (per-kernel events and rooflines, "
+                         "per-pair costs, CPU baseline, pinned sha256, decompress, k=21, e2e, T2T); off: the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's record streams to DIR as .npy (float32 / float64, < 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.only_steps = args.no_check = True
     if args.only_steps:
         args.no_decomp = args.no_e2e = args.no_t2t = args.no_k21 = args.no_prof = args.no_cpu_baseline = True
 
@@ -733,6 +794,21 @@ def main() -> None:
     dt = timed_region(step, args.steps, 0, world, torch.cuda.synchronize, dev)
     prof_dom = lanes[0].ctx.profile_get()
     lanes[0].ctx.profile(False)
+
+    # ---- the last timed step's record streams on rank 0, for the dump and the pin check
+    streams = None
+    if args.dump_outputs or not args.no_check:
+        torch.cuda.synchronize()
+        if world > 1:
+            got = gather.result()
+            streams = {n: t.cpu().numpy().tobytes() for n, t in got.items()} if got is not None else None
+        else:
+            streams = gather_streams(results, order, 1, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(streams, args.dump_outputs)
+        log(f"bench: {dumped['streams']} record streams written to {dumped['dir']} ({dumped['bytes']:,} bytes)")
+
     prof_all = {}
     if not args.no_prof:
         lanes[0].ctx.profile(True)
@@ -766,12 +842,6 @@ def main() -> None:
     # ---- parity: every chromosome's record stream against the reference's pinned sha256
     parity = None
     if not args.no_check:
-        torch.cuda.synchronize()
-        if world > 1:
-            got = gather.result()
-            streams = {n: t.cpu().numpy().tobytes() for n, t in got.items()} if got is not None else None
-        else:
-            streams = gather_streams(results, order, 1, dev)
         if rank == 0:
             pins = load_manifest() if args.workload == "genome" else {}
             parity = check_pins(streams, pins)
@@ -931,6 +1001,8 @@ def main() -> None:
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_step,
+            "full": args.full,
+            "dumped_outputs": dumped,
             "higher_is_better": True,
             "scaling": "strong" if args.workload == "genome" else "weak",
             "vs_baseline": None,

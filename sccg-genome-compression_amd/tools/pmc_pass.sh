@@ -3,6 +3,7 @@
 #   tools/pmc_pass.sh <tag> "<counters (one pass's worth)>" [extra bench.py args]
 set -eo pipefail
 TAG=$1; CTRS=$2; shift 2
+set -- --full "$@"   # every leg's kernels, as the summaries expect
 mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc $CTRS --output-format csv -d gpurun_out/pmc/$TAG -o run -- \

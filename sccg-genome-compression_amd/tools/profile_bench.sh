@@ -12,7 +12,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 TOOLS=sccg-genome-compression_amd/tools
-BENCH="bench.py --no-cpu-baseline --no-check $*"
+BENCH="bench.py --full --no-cpu-baseline --no-check $*"
 
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run \
     -- python3 $BENCH --steps 5 --warmup 1 > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"

@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 T=sccg-genome-compression_amd/tools
-BENCH="bench.py --no-cpu-baseline --no-check --no-decomp --no-e2e --no-t2t --steps 2 --warmup 1 $*"
+BENCH="bench.py --full --no-cpu-baseline --no-check --no-decomp --no-e2e --no-t2t --steps 2 --warmup 1 $*"
 pass() {   # name, counters
   timeout -s KILL 90 rocprofv3 --pmc $2 --output-format csv -d "$OUT/$1" -o run -- python3 $BENCH > /dev/null 2> "$OUT/$1.err"
   F=$(find "$OUT/$1" -name '*counter_collection.csv' | head -n 1)

@@ -197,6 +197,41 @@ def test_bench_step_gather_no_host_sync_gloo_world2():
     assert r0["refused"] and r1["refused"]
 
 
+def test_dump_outputs_whole_then_fixed_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): small streams are written whole as float32; larger ones
+    as a sample at the same positions in every call, with per-block sums over every byte, so a byte
+    changed outside the sample still changes the dump."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    streams = {n: rng.integers(0, 256, size=ln, dtype=np.uint8).tobytes()
+               for n, ln in (("chr1", 3 * bench.DUMP_BLOCK + 17), ("chr2", 5000), ("chrM", 0))}
+    info = bench.dump_outputs(streams, str(tmp_path / "whole"))
+    assert info["streams"] == 3 and not info["sampled"]
+    for n, s in streams.items():
+        a = np.load(tmp_path / "whole" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.astype(np.uint8).tobytes() == s
+    assert np.load(tmp_path / "whole" / "lengths.npy").tolist() == [len(streams[n]) for n in sorted(streams)]
+    b = np.load(tmp_path / "whole" / "chr1_blocks.npy")
+    assert b.dtype == np.float64 and b.shape == (4, 2) and b[:, 0].sum() == sum(streams["chr1"])
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ELEMS", 1000)
+    one = bench.dump_outputs(streams, str(tmp_path / "a"))
+    bench.dump_outputs(streams, str(tmp_path / "b"))
+    assert one["sampled"]
+    total = sum(len(s) for s in streams.values())
+    for n, s in streams.items():
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        assert len(a) == (max(1, len(s) * 1000 // total) if s else 0)
+    assert one["bytes"] == sum(os.path.getsize(p) - 128 for p in (tmp_path / "a").iterdir())
+    # one byte changed: the lengths and most likely the sample stay, the block sums do not
+    changed = dict(streams, chr1=streams["chr1"][:100] + bytes([streams["chr1"][100] ^ 1]) + streams["chr1"][101:])
+    bench.dump_outputs(changed, str(tmp_path / "c"))
+    assert not np.array_equal(np.load(tmp_path / "a" / "chr1_blocks.npy"), np.load(tmp_path / "c" / "chr1_blocks.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "chr2_blocks.npy"), np.load(tmp_path / "c" / "chr2_blocks.npy"))
+
+
 def test_job_models_say_what_they_count():
     """roofline_job's design model (what this design moves: byte copies, no k-mer index) and
     SURVEY §8(d)'s model (2-bit packing, a 4|R'| CSR index this design never builds)."""
