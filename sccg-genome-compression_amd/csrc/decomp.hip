@@ -118,10 +118,8 @@ __global__ void k_run_items_parse(const uint8_t* __restrict__ s, int64_t n, cons
 // of a parenthesis max-scan, an item-rank scan and three prefix sums (decompression.cpp:126-207 per
 // item, running start, sorted).
 // ---------------------------------------------------------------------------------------------
-#ifndef SCCG_RL_LANE
-#define SCCG_RL_LANE 8   // (16: ~5 us slower on the chr1 reconstruction, more serial bytes per lane)
-#endif
-constexpr int RL_LANE = SCCG_RL_LANE, RL_TILE = 64 * RL_LANE, RL_BEHIND = 32, RL_AHEAD = 64;
+constexpr int RL_LANE = 8;   // (16: ~5 us slower on the chr1 reconstruction, more serial bytes per lane)
+constexpr int RL_TILE = 64 * RL_LANE, RL_BEHIND = 32, RL_AHEAD = 64;
 constexpr int RL_STAGE = RL_BEHIND + RL_TILE + RL_AHEAD;
 
 // the wave's staged bytes: global positions [t0 - RL_BEHIND, t0 + tile + RL_AHEAD), 0 outside [0, n)
@@ -424,73 +422,17 @@ __global__ void k_n_check(const int32_t* __restrict__ ns, const int32_t* __restr
 // ---------------------------------------------------------------------------------------------
 // record line
 // ---------------------------------------------------------------------------------------------
-// per byte: output contribution (literal 1, token l, else 0) and token delta (tokens only)
-__global__ void k_tok_parse(const uint8_t* __restrict__ s, int64_t n, const int64_t* __restrict__ lp,
-                            int64_t* __restrict__ contrib, int64_t* __restrict__ dlt, int32_t* __restrict__ err) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint8_t c = s[i];
-        const bool inside = lp[i] >= 0 && s[lp[i]] == '(';
-        int64_t cb = 0, d = 0;
-        if (c == '(') {
-            int64_t comma = -1, close = -1;
-            for (int64_t q = i + 1; q < n && q < i + 32; q++) {
-                if (s[q] == ',' && comma < 0) comma = q;
-                if (s[q] == ')') { close = q; break; }
-                if (s[q] == '(') break;
-            }
-            int64_t l = 0;
-            if (!(comma > 0 && close > comma && parse_int(s, n, i + 1, comma, &d) && parse_int(s, n, comma + 1, close, &l)) || l < 0)
-                atomicOr(err, 1);
-            cb = l;
-        } else if (c == ')') {
-            cb = inside ? 0 : 1;             // a ')' outside a token is a literal (decompression.cpp:231-234)
-        } else if (!inside) {
-            cb = 1;
-        }
-        contrib[i] = cb;
-        dlt[i] = d;
-    }
-}
-
-// absolute p = running sum of deltas over tokens (decompression.cpp:220-222); range check :223
-__global__ void k_tok_check(const uint8_t* __restrict__ s, int64_t n, const int64_t* __restrict__ dsum,
-                            const int64_t* __restrict__ dlt, const int64_t* __restrict__ contrib,
-                            const int64_t* __restrict__ d_nref, int32_t* __restrict__ err) {
-    const int64_t nref = *d_nref;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        if (s[i] != '(') continue;
-        const int64_t p = dsum[i] + dlt[i];
-        if (p < 0 || p + contrib[i] > nref) atomicOr(err, 2);
-    }
-}
-
 constexpr int WPB = 4;
-// 16 bytes from any byte address: one global_load_dwordx4 (gfx950 runs in unaligned access mode;
-// SCCG_UNALIGNED_LD=0: five dword loads combined with v_alignbyte, as before round 6)
-#ifndef SCCG_UNALIGNED_LD
-#define SCCG_UNALIGNED_LD 1
-#endif
+// 16 bytes from any byte address: one global_load_dwordx4 (gfx950 runs in unaligned access mode)
 __device__ __forceinline__ uint4 load16u(const uint8_t* __restrict__ p) {
     uint4 v;
-    if (SCCG_UNALIGNED_LD) {
-        __builtin_memcpy(&v, p, 16);
-    } else {
-        const uint32_t* sa = reinterpret_cast<const uint32_t*>((uintptr_t)p & ~(uintptr_t)3);
-        const unsigned sh = (unsigned)((uintptr_t)p & 3);
-        uint32_t w[5];
-#pragma unroll
-        for (int i = 0; i < 5; i++) w[i] = sa[i];
-        v = make_uint4(__builtin_amdgcn_alignbyte(w[1], w[0], sh), __builtin_amdgcn_alignbyte(w[2], w[1], sh),
-                       __builtin_amdgcn_alignbyte(w[3], w[2], sh), __builtin_amdgcn_alignbyte(w[4], w[3], sh));
-    }
+    __builtin_memcpy(&v, p, 16);
     return v;
 }
 // dst[0, l) = src[0, l) by one wave: bytes up to dst's next 16-byte boundary and after its last one
 // one per lane, the rest 16 bytes per lane as aligned stores of (unaligned) 16-byte source loads.
 // The source may be read up to 19 bytes past src + l (the reference buffers carry 64 bytes of slack).
-#ifndef WC_DEPTH
-#define WC_DEPTH 2
-#endif
+constexpr int WC_DEPTH = 2;
 __device__ __forceinline__ void wave_copy_body(uint4* __restrict__ d, const uint8_t* __restrict__ s0, int64_t nb, int64_t from,
                                                int lane);
 __device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
@@ -527,39 +469,6 @@ __device__ __forceinline__ void wave_copy_body(uint4* __restrict__ d, const uint
     }
 }
 
-__global__ __launch_bounds__(SCCG_BLOCK) void k_tok_fill(const uint8_t* __restrict__ s, int64_t n,
-                                                         const int64_t* __restrict__ lp, const int64_t* __restrict__ off,
-                                                         const int64_t* __restrict__ dsum, const int64_t* __restrict__ dlt,
-                                                         const int64_t* __restrict__ contrib, const uint8_t* __restrict__ R,
-                                                         uint8_t* __restrict__ dec) {
-    // one wave per 64-byte stretch of the record line; tokens are copied by the whole wave
-    const int64_t base = ((int64_t)blockIdx.x * WPB + wave_in_block()) * 64;
-    if (base >= n) return;
-    const int lane = lane_id();
-    const int64_t i = base + lane;
-    bool tok = false;
-    int64_t p = 0, l = 0, o = 0;
-    if (i < n) {
-        const uint8_t c = s[i];
-        const bool inside = lp[i] >= 0 && s[lp[i]] == '(';
-        if (c == '(') {
-            tok = true;
-            p = dsum[i] + dlt[i];
-            l = contrib[i];
-            o = off[i];
-        } else if (!inside) {
-            dec[off[i]] = c;   // literals, a stray ')' included
-        }
-    }
-    unsigned long long tm = __ballot(tok);
-    while (tm) {
-        const int j = __ffsll((long long)tm) - 1;
-        tm &= tm - 1;
-        const int64_t pj = __shfl(p, j), lj = __shfl(l, j), oj = __shfl(o, j);
-        wave_copy(dec + oj, R + pj, lj, lane);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // record line, per 64-byte block (the usual path).  A token "(dp,l)" is at most 25 bytes, so the
 // "inside a token" state at a block's first byte follows from the last parenthesis before it (the
@@ -574,7 +483,7 @@ constexpr int TK_B = 64;   // record bytes per block (one lane in pass 1, one wa
 
 __global__ __launch_bounds__(256) void k_tok_blocks(const uint8_t* __restrict__ s, int64_t n, int64_t* __restrict__ bin,
                                                     int64_t* __restrict__ bcontrib, int64_t* __restrict__ bdelta,
-                                                    int32_t* __restrict__ err, int64_t* __restrict__ btok) {
+                                                    int32_t* __restrict__ err) {
     // one wave per 1 KiB tile (16 bytes per lane, staged in LDS); 4 lanes make one 64-byte block
     constexpr int TL = 16, TT = 64 * TL;
     __shared__ uint8_t stage[4][RL_BEHIND + TT + RL_AHEAD];
@@ -586,7 +495,7 @@ __global__ __launch_bounds__(256) void k_tok_blocks(const uint8_t* __restrict__ 
     const int64_t a = t0 + (int64_t)lane * TL;
     bool inside = rl_lane_inside(v, a, TL);
     const bool in0 = inside;
-    int64_t cs = 0, ds = 0, tk = 0;
+    int64_t cs = 0, ds = 0;
     bool bad = false;
     for (int64_t i = a; i < a + TL && i < n; i++) {
         const uint8_t c = v.at(i);
@@ -601,8 +510,6 @@ __global__ __launch_bounds__(256) void k_tok_blocks(const uint8_t* __restrict__ 
             if (!(comma > 0 && close > comma && parse_int_v(v, i + 1, comma, &d) && parse_int_v(v, comma + 1, close, &l)) ||
                 l < 0)
                 bad = true;
-            else
-                tk++;
             cs += l;
             ds += d;
             inside = true;
@@ -618,15 +525,12 @@ __global__ __launch_bounds__(256) void k_tok_blocks(const uint8_t* __restrict__ 
     cs += __shfl_xor(cs, 2, 64);
     ds += __shfl_xor(ds, 1, 64);
     ds += __shfl_xor(ds, 2, 64);
-    tk += __shfl_xor(tk, 1, 64);
-    tk += __shfl_xor(tk, 2, 64);
     static_assert(4 * TL == TK_B, "four lanes per block");
     const int64_t b = t * (TT / TK_B) + (lane >> 2);
     if ((lane & 3) == 0 && b * TK_B < n) {
         bin[b] = in0;
         bcontrib[b] = cs;
         bdelta[b] = ds;
-        if (btok) btok[b] = tk;
     }
 }
 
@@ -701,79 +605,6 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_tok_fill2(const uint8_t* __restr
     }
 }
 
-// Token table of the fused reconstruction (opt-in, SCCG_DC_FUSED=1): instead of copying bytes into a decoded
-// buffer that the formatter reads back (k_tok_fill2), one wave per 64-byte block writes each token's
-// decoded offset o, absolute reference position p, length l and the record offset r right after its
-// ')' (decompression.cpp:210-236).  Entry 0 is a sentinel (0, 0, 0, 0) for the literals before the
-// first token; token j of the line is entry 1 + j.  Decoded byte x then lies in entry t = the last
-// with o_t <= x: it is R'[p_t + x - o_t] when x < o_t + l_t, else the literal rec[r_t + x - o_t - l_t]
-// (between a token's ')' and the next '(' every byte is a literal, :231-236).  Needs no R', so it
-// runs beside the reference strip; the range check (:223-229) is k_tok_range, after the strip.
-__global__ __launch_bounds__(SCCG_BLOCK) void k_tok_emit(const uint8_t* __restrict__ s, int64_t n,
-                                                         const int64_t* __restrict__ bin, const int64_t* __restrict__ boff,
-                                                         const int64_t* __restrict__ bdsum, const int64_t* __restrict__ btoff,
-                                                         DcTokTab tk) {
-    __shared__ uint8_t stg[WPB][2 * TK_B];
-    const int64_t b = (int64_t)blockIdx.x * WPB + wave_in_block();
-    const int64_t base = b * TK_B;
-    if (base >= n) return;
-    const int lane = lane_id();
-    const int64_t i = base + lane;
-    uint8_t* st = stg[wave_in_block()];
-    const uint8_t c = i < n ? s[i] : (uint8_t)',';
-    st[lane] = c;
-    st[TK_B + lane] = i + TK_B < n ? s[i + TK_B] : (uint8_t)0;
-    wave_sync();
-    const RlView v{st - RL_BEHIND, base, n, TK_B};
-    const bool par = i < n && (c == '(' || c == ')');
-    const unsigned long long pm = __ballot(par) & ((1ull << lane) - 1ull);
-    const bool inside = pm ? st[63 - __clzll((long long)pm)] == '(' : bin[b] != 0;
-    int64_t contrib = 0, d = 0, close = -1;
-    bool tok = false;
-    if (i < n) {
-        if (c == '(') {
-            int64_t comma = -1, l = 0;
-            for (int64_t q = i + 1; q < n && q < i + 32; q++) {
-                const uint8_t cq = v.at(q);
-                if (cq == ',' && comma < 0) comma = q;
-                if (cq == ')') { close = q; break; }
-                if (cq == '(') break;
-            }
-            if (comma > 0 && close > comma && parse_int_v(v, i + 1, comma, &d) && parse_int_v(v, comma + 1, close, &l) && l >= 0) {
-                tok = true;
-                contrib = l;
-            }
-        } else if (c == ')') {
-            contrib = inside ? 0 : 1;
-        } else if (!inside) {
-            contrib = 1;
-        }
-    }
-    const int64_t o = boff[b] + wave_incl_add(contrib) - contrib;
-    const int64_t p = bdsum[b] + wave_incl_add(d);   // running p, this token included
-    const unsigned long long tm = __ballot(tok);
-    if (tok) {
-        const int64_t e = 1 + btoff[b] + __popcll(tm & ((1ull << lane) - 1ull));
-        tk.o[e] = o;
-        tk.p[e] = p;
-        tk.l[e] = contrib;
-        tk.r[e] = close + 1;
-    }
-    if (b == 0 && lane == 0) { tk.o[0] = 0; tk.p[0] = 0; tk.l[0] = 0; tk.r[0] = 0; }
-}
-
-// d_err bit 2 for a token beyond the reference (p < 0 or p + l > |R'|, decompression.cpp:223-229)
-__global__ void k_tok_range(DcTokTab tk, const int64_t* __restrict__ d_ntok, const int64_t* __restrict__ d_nref,
-                            int32_t* __restrict__ err) {
-    const int64_t nt = *d_ntok, nref = *d_nref;
-    bool bad = false;
-    for (int64_t t = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t <= nt; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = tk.p[t], l = tk.l[t];
-        if (p < 0 || p + l > nref) bad = true;
-    }
-    if (bad) atomicOr(err, 2);
-}
-
 // ---------------------------------------------------------------------------------------------
 // output: header '\n' then result wrapped at 50 columns + final '\n'
 // ---------------------------------------------------------------------------------------------
@@ -787,13 +618,6 @@ __device__ __forceinline__ int64_t first_run_ending_after(const int32_t* st, con
     return a;
 }
 
-// A block owns FSPAN consecutive sequence positions.  Their decoded bytes (one contiguous range
-// of dec, N positions excluded) are loaded into LDS with stride-1 reads, every thread formats FPER
-// positions into the block's LDS copy of its output range (N runs, lowercase runs, a '\n' after
-// every 50th base but the last), and the block stores that range with stride-1 writes.  (A
-// thread-per-64-positions writer straight to HBM, lanes 64 bytes apart, took 4.6 ms for a
-// chr1-sized FASTA.)
-constexpr int FPER = 16, FSPAN = 256 * FPER;
 // N positions before j (j inside an N run: those of the run before j included), given
 // r = first_run_ending_after(ns, nl, nn, j)
 __device__ __forceinline__ int64_t n_before_at(const int32_t* ns, const int32_t* nl, const int64_t* ncum, int64_t nn,
@@ -802,29 +626,8 @@ __device__ __forceinline__ int64_t n_before_at(const int32_t* ns, const int32_t*
     return nn ? ncum[nn - 1] + nl[nn - 1] : 0;
 }
 
-// Span boundaries J_b = min(b * FSPAN, nres), b = 0..nspan: the first N run and the first
-// lowercase run ending after J_b, and J_b minus the N positions before it (the decoded-byte offset
-// of J_b).  One thread per (boundary, run list), all independent: the dependent binary-search loads
-// overlap across the grid instead of sitting at the head of every format block (a per-block search
-// chain of ~36 loads x 30 block generations took 0.79 ms of a chr1 reconstruction).
-__global__ void k_span_index(int64_t nres, int64_t nspan, const int32_t* __restrict__ ns, const int32_t* __restrict__ nl,
-                             const int64_t* __restrict__ ncum, int64_t nn, const int32_t* __restrict__ ls,
-                             const int32_t* __restrict__ ll, int64_t nlr, int64_t* __restrict__ tab) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * (nspan + 1); i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = i >> 1;
-        const int64_t J = b * FSPAN < nres ? b * FSPAN : nres;
-        if (i & 1) {
-            tab[3 * b + 2] = first_run_ending_after(ls, ll, nlr, J);
-        } else {
-            const int64_t r = first_run_ending_after(ns, nl, nn, J);
-            tab[3 * b + 0] = J - n_before_at(ns, nl, ncum, nn, r, J);
-            tab[3 * b + 1] = r;
-        }
-    }
-}
-
-// Run-list views for format_positions: starts, ends and (N runs) the N count before each run,
-// read from the span's LDS copies or from the global lists.
+// Run-list view for format_out16: starts, ends and (N runs) the N count before each run, read
+// from the block's LDS copies (GlobalRunsAt: from the global lists).
 struct LdsRuns {
     const int32_t* s;
     const int32_t* e;
@@ -833,48 +636,6 @@ struct LdsRuns {
     __device__ int64_t en(int64_t r) const { return e[r]; }
     __device__ int64_t nb(int64_t r) const { return b[r]; }
 };
-struct GlobalRuns {
-    const int32_t* s;
-    const int32_t* l;
-    const int64_t* b;
-    __device__ int64_t st(int64_t r) const { return s[r]; }
-    __device__ int64_t en(int64_t r) const { return (int64_t)s[r] + l[r]; }
-    __device__ int64_t nb(int64_t r) const { return b[r]; }
-};
-
-// Formats positions [j0, j0 + FPER) of a span (j < J1) into sout; rn / rl enter as the first
-// N / lowercase run ending after j0 (runs past the views' counts: none left, ntot N before).
-template <typename V>
-__device__ __forceinline__ void format_positions(int64_t j0, int64_t J1, int64_t nres, int64_t O0, int64_t dbase,
-                                                 const uint8_t* sdec, uint8_t* sout, V N, int64_t nn, int64_t ntot, V L,
-                                                 int64_t nlr, int64_t rn, int64_t rl) {
-    int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot, l_s = INT64_MAX, l_e = INT64_MAX;
-    if (rn < nn) { n_s = N.st(rn); n_e = N.en(rn); n_b = N.nb(rn); }
-    if (rl < nlr) { l_s = L.st(rl); l_e = L.en(rl); }
-    // output offset of j = j + j / 50 - O0, kept as a running column (no 64-bit division per base)
-    int64_t o = j0 + j0 / 50 - O0;
-    int col = (int)(j0 % 50);
-    const int64_t je = j0 + FPER < J1 ? j0 + FPER : J1;
-    for (int64_t j = j0; j < je; j++) {
-        while (j >= n_e) {
-            rn++;
-            if (rn < nn) { n_s = N.st(rn); n_e = N.en(rn); n_b = N.nb(rn); }
-            else { n_s = n_e = INT64_MAX; n_b = ntot; }
-        }
-        while (j >= l_e) {
-            rl++;
-            if (rl < nlr) { l_s = L.st(rl); l_e = L.en(rl); }
-            else l_s = l_e = INT64_MAX;
-        }
-        uint8_t c = j >= n_s ? (uint8_t)'N' : sdec[j - n_b - dbase];
-        if (j >= l_s) c = c_tolower(c);
-        sout[o++] = c;
-        if (++col == 50) {
-            col = 0;
-            if (j != nres - 1) sout[o++] = '\n';
-        }
-    }
-}
 
 // first r in [a, b) with V::en(r) > j, ends ascending
 template <typename V>
@@ -886,86 +647,6 @@ __device__ __forceinline__ int64_t first_end_after(const V& v, int64_t a, int64_
     return a;
 }
 
-// One block per span.  The span's decoded bytes (dword loads), and when they are few (<= FRUNS
-// each, the usual case) the N and lowercase runs it touches, are staged in LDS in one round trip
-// behind the span table; every thread then formats FPER positions from LDS only, and the block
-// stores its output range with dword stores.  Spans with dense run alternation read the run
-// lists from global memory instead.
-constexpr int FRUNS = 384;
-__global__ __launch_bounds__(256) void k_format_span(const uint8_t* __restrict__ dec, int64_t nres,
-                                                     const int32_t* __restrict__ ns, const int32_t* __restrict__ nl,
-                                                     const int64_t* __restrict__ ncum, int64_t nn,
-                                                     const int32_t* __restrict__ ls, const int32_t* __restrict__ ll,
-                                                     int64_t nlr, const int64_t* __restrict__ tab, uint8_t* __restrict__ out) {
-    __shared__ uint32_t sdec_w[FSPAN / 4 + 2];
-    __shared__ uint8_t sout[FSPAN + FSPAN / 50 + 8];
-    __shared__ int32_t s_ns[FRUNS], s_ne[FRUNS], s_ls[FRUNS], s_le[FRUNS];
-    __shared__ int64_t s_nb[FRUNS];
-    __shared__ int64_t st[7];
-    const int64_t b = blockIdx.x;
-    const int64_t J0 = b * FSPAN;
-    if (J0 >= nres) return;
-    const int64_t J1 = J0 + FSPAN < nres ? J0 + FSPAN : nres;
-    const int tid = threadIdx.x;
-    if (tid < 6) st[tid] = tab[3 * b + tid];
-    if (tid == 6) st[6] = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
-    __syncthreads();
-    // the runs this span touches lie in [first(J0), first(J1)] (first = first run ending after)
-    const int64_t d0 = st[0], dn = st[3] - d0;
-    const int64_t n_lo = st[1], n_hi = st[4] < nn ? st[4] + 1 : nn;
-    const int64_t l_lo = st[2], l_hi = st[5] < nlr ? st[5] + 1 : nlr;
-    const int64_t ntot = st[6];
-    const bool lds_runs = n_hi - n_lo <= FRUNS && l_hi - l_lo <= FRUNS;
-    const int64_t a0 = d0 & ~(int64_t)3;
-    const int64_t nw = (d0 + dn - a0 + 3) >> 2;
-    const uint32_t* decw = reinterpret_cast<const uint32_t*>(dec + a0);
-    for (int64_t i = tid; i < nw; i += 256) sdec_w[i] = decw[i];
-    if (lds_runs) {
-        for (int64_t r = n_lo + tid; r < n_hi; r += 256) {
-            const int32_t x = ns[r];
-            s_ns[r - n_lo] = x;
-            s_ne[r - n_lo] = x + nl[r];
-            s_nb[r - n_lo] = ncum[r];
-        }
-        for (int64_t r = l_lo + tid; r < l_hi; r += 256) {
-            const int32_t x = ls[r];
-            s_ls[r - l_lo] = x;
-            s_le[r - l_lo] = x + ll[r];
-        }
-    }
-    __syncthreads();
-    const uint8_t* sdec = reinterpret_cast<const uint8_t*>(sdec_w);
-    const int64_t O0 = J0 + J0 / 50;
-    const int64_t jl = J1 - 1;
-    const int64_t On = jl + jl / 50 + 1 + ((jl % 50 == 49 && jl != nres - 1) ? 1 : 0) - O0;
-    const int64_t j0 = J0 + (int64_t)tid * FPER;
-    if (j0 < J1) {
-        if (lds_runs) {
-            const int64_t cn = n_hi - n_lo, cl = l_hi - l_lo;
-            const LdsRuns N{s_ns, s_ne, s_nb}, L{s_ls, s_le, nullptr};
-            format_positions(j0, J1, nres, O0, a0, sdec, sout, N, cn, ntot, L, cl, first_end_after(N, 0, cn, j0),
-                             first_end_after(L, 0, cl, j0));
-        } else {
-            const GlobalRuns N{ns, nl, ncum}, L{ls, ll, nullptr};
-            format_positions(j0, J1, nres, O0, a0, sdec, sout, N, nn, ntot, L, nlr, first_end_after(N, n_lo, n_hi, j0),
-                             first_end_after(L, l_lo, l_hi, j0));
-        }
-    }
-    __syncthreads();
-    // store [O0, O0 + On): bytes up to the first 4-byte boundary and after the last, dwords between
-    uint8_t* o = out + O0;
-    const int64_t h = ((4 - ((uintptr_t)o & 3)) & 3) < On ? ((4 - ((uintptr_t)o & 3)) & 3) : On;
-    const int64_t nbw = (On - h) >> 2;
-    const int64_t t0 = h + (nbw << 2);
-    if (tid < h) o[tid] = sout[tid];
-    if (tid < On - t0) o[t0 + tid] = sout[t0 + tid];
-    uint32_t* ow = reinterpret_cast<uint32_t*>(o + h);
-    for (int64_t i = tid; i < nbw; i += 256) {
-        const uint8_t* q = sout + h + 4 * i;
-        ow[i] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Output-centric formatter (the usual path).  A block owns OB = 4096 bytes of the OUTPUT, aligned
 // to 16 bytes in memory; every thread builds 16 output bytes in registers and stores them with one
@@ -974,26 +655,20 @@ __global__ __launch_bounds__(256) void k_format_span(const uint8_t* __restrict__
 // byte at j minus the N positions before j, lowercased inside a lowercase run
 // (decompression.cpp:241-274).  The block's decoded bytes and the runs it touches are staged in
 // LDS (runs from the global lists when they are more than OFRUNS); a thread finds its first runs by
-// binary search in LDS and then walks them.  (The position-centric k_format_span wrote each
-// position's byte to LDS, 16 bytes apart per lane, and copied the line-broken range out again.)
+// binary search in LDS and then walks them.
 // ---------------------------------------------------------------------------------------------
-#ifndef SCCG_OFRUNS
-#define SCCG_OFRUNS 384
-#endif
-constexpr int OPT = 16, OB = 256 * OPT, OFRUNS = SCCG_OFRUNS;   // (a block with more runs takes the global-runs path)
-constexpr int TW = 5;   // k_out_index entries per block boundary
-constexpr int FMT_U_DEFAULT = 4;   // (U = 1 / 2 / 4 on one box, chr1: 0.638-0.647 / 0.634-0.639 / 0.624-0.626 ms;
-                                    //  round 6, U = 8: 42 KiB of LDS per block, 0.677-0.682 against 0.614-0.638)
-constexpr bool FMT_NT_DEFAULT = false;
+constexpr int OPT = 16, OB = 256 * OPT, OFRUNS = 384;   // (a block with more runs takes the global-runs path)
+constexpr int TW = 5;      // k_out_index entries per block boundary (the fifth is a spare: no one reads it)
+constexpr int FMT_U = 4;   // (U = 1 / 2 / 4 on one box, chr1: 0.638-0.647 / 0.634-0.639 / 0.624-0.626 ms;
+                           //  round 6, U = 8: 42 KiB of LDS per block, 0.677-0.682 against 0.614-0.638)
 
-// Block boundaries: output offset o_b = o_first + b * OB clamped to [0, total]; its position
+// Block boundaries: output offset o_b = o_first + b * ob clamped to [0, total]; its position
 // j_b = o - o / 51; per boundary [decoded offset d_b of j_b, first N run and first lowercase run
-// ending after j_b, j_b, and (fused path, tko given) the token-table entry holding d_b: the last
-// with o_t <= d_b].  One thread per (boundary, run list).
+// ending after j_b, j_b].  One thread per (boundary, run list).
 __global__ void k_out_index(int64_t nres, int64_t total, int64_t o_first, int64_t nblk, int64_t ob, const int32_t* __restrict__ ns,
                             const int32_t* __restrict__ nl, const int64_t* __restrict__ ncum, int64_t nn,
                             const int32_t* __restrict__ ls, const int32_t* __restrict__ ll, int64_t nlr,
-                            const int64_t* __restrict__ tko, const int64_t* __restrict__ d_ntok, int64_t* __restrict__ tab) {
+                            int64_t* __restrict__ tab) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * (nblk + 1); i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = i >> 1;
         int64_t o = o_first + b * ob;
@@ -1007,31 +682,17 @@ __global__ void k_out_index(int64_t nres, int64_t total, int64_t o_first, int64_
             tab[TW * b + 0] = d;
             tab[TW * b + 1] = r;
             tab[TW * b + 3] = J;
-            if (tko) {
-                int64_t lo = 0, hi = *d_ntok;   // entry 0 (o = 0) qualifies
-                while (lo < hi) {
-                    const int64_t m = (lo + hi + 1) >> 1;
-                    if (tko[m] <= d) lo = m; else hi = m - 1;
-                }
-                tab[TW * b + 4] = lo;
-            }
         }
     }
 }
 
-template <bool NT>
 __device__ __forceinline__ void store16(uint8_t* p, uint64_t lo, uint64_t hi) {
-    if (NT) {   // streaming store: the output is not read again by this kernel
-        __builtin_nontemporal_store(lo, reinterpret_cast<uint64_t*>(p));
-        __builtin_nontemporal_store(hi, reinterpret_cast<uint64_t*>(p) + 1);
-    } else {
-        *reinterpret_cast<uint4*>(p) = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
-    }
+    *reinterpret_cast<uint4*>(p) = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
 }
 
 // format_out16 with the position (j, col of oc = max(o0, 0)) and the first N / lowercase runs
 // ending after j (rn, rl) given by the caller
-template <typename V, bool NT = false>
+template <typename V>
 __device__ __forceinline__ void format_out16_at(int64_t o0, int64_t total, const uint8_t* sdec, int64_t dbase, const V& N,
                                                 int64_t cn, int64_t ntot, const V& L, int64_t cl, uint8_t* out, int64_t j,
                                                 int col, int64_t rn, int64_t rl) {
@@ -1112,7 +773,7 @@ __device__ __forceinline__ void format_out16_at(int64_t o0, int64_t total, const
                 if (knl < 8) slo = (slo & ~(0xffull << (8 * knl))) | ((uint64_t)'\n' << (8 * knl));
                 else shi = (shi & ~(0xffull << (8 * (knl - 8)))) | ((uint64_t)'\n' << (8 * (knl - 8)));
             }
-            store16<NT>(out + o0, slo, shi);
+            store16(out + o0, slo, shi);
             return;
         }
     }
@@ -1141,13 +802,13 @@ __device__ __forceinline__ void format_out16_at(int64_t o0, int64_t total, const
         else hi |= (uint64_t)c << (8 * (k - 8));
     }
     if (k0 == 0 && k1 == OPT) {
-        store16<NT>(out + o0, lo, hi);
+        store16(out + o0, lo, hi);
     } else {
         for (int k = k0; k < k1; k++) out[o0 + k] = (uint8_t)((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8))) & 0xff);
     }
 }
 
-template <typename V, bool NT = false>
+template <typename V>
 __device__ __forceinline__ void format_out16(int64_t o0, int64_t total, int64_t nres, const uint8_t* sdec, int64_t dbase,
                                              const V& N, int64_t cn, int64_t ntot, const V& L, int64_t cl, uint8_t* out) {
     (void)nres;
@@ -1155,8 +816,8 @@ __device__ __forceinline__ void format_out16(int64_t o0, int64_t total, int64_t 
     if (oc >= total || o0 + OPT <= 0) return;
     const int64_t j = oc - oc / 51;
     const int col = (int)(oc % 51);
-    format_out16_at<V, NT>(o0, total, sdec, dbase, N, cn, ntot, L, cl, out, j, col, first_end_after(N, 0, cn, j),
-                           first_end_after(L, 0, cl, j));
+    format_out16_at(o0, total, sdec, dbase, N, cn, ntot, L, cl, out, j, col, first_end_after(N, 0, cn, j),
+                    first_end_after(L, 0, cl, j));
 }
 
 // first r in [0, c) with e[r] > j over an LDS run list: short lists (a tile holds a few runs) by a
@@ -1187,8 +848,7 @@ struct GlobalRunsAt {
 };
 
 // U: 16-byte outputs per thread (a block owns U * OB output bytes: fewer, larger dependent load
-// phases per byte); NT: streaming stores for the output.
-template <int U, bool NT>
+// phases per byte)
 __global__ __launch_bounds__(256) void k_format_out(const uint8_t* __restrict__ dec, int64_t nres, int64_t total, int64_t o_first,
                                                     const int32_t* __restrict__ ns, const int32_t* __restrict__ nl,
                                                     const int64_t* __restrict__ ncum, int64_t nn,
@@ -1196,6 +856,7 @@ __global__ __launch_bounds__(256) void k_format_out(const uint8_t* __restrict__ 
                                                     int64_t nlr, const int64_t* __restrict__ tab, uint8_t* __restrict__ out) {
     // the tile's decoded bytes from a 16-byte-aligned base, 16 bytes per thread and load, with
     // 16 bytes of slack for format_out16's unaligned 16-byte reads (dec holds >= 64 bytes of slack)
+    constexpr int U = FMT_U;
     __shared__ uint4 sdec4[(U * OB + 64) / 16];
     __shared__ int32_t s_ns[OFRUNS], s_ne[OFRUNS], s_ls[OFRUNS], s_le[OFRUNS];
     __shared__ int64_t s_nb[OFRUNS];
@@ -1251,281 +912,13 @@ __global__ __launch_bounds__(256) void k_format_out(const uint8_t* __restrict__ 
             const int col = q - 51 * nl51;
             const int32_t jr = (int32_t)j;   // (positions are int32 in the run lists)
             const LdsRuns N{s_ns, s_ne, s_nb}, L{s_ls, s_le, nullptr};
-            format_out16_at<LdsRuns, NT>(o0, total, sdec, a0, N, n_hi - n_lo, ntot, L, l_hi - l_lo, out, j, col,
-                                         lds_first_end_after(s_ne, (int32_t)(n_hi - n_lo), jr),
-                                         lds_first_end_after(s_le, (int32_t)(l_hi - l_lo), jr));
+            format_out16_at(o0, total, sdec, a0, N, n_hi - n_lo, ntot, L, l_hi - l_lo, out, j, col,
+                            lds_first_end_after(s_ne, (int32_t)(n_hi - n_lo), jr),
+                            lds_first_end_after(s_le, (int32_t)(l_hi - l_lo), jr));
         } else {
             const GlobalRunsAt N{ns, nl, ncum, n_lo}, L{ls, ll, nullptr, l_lo};
-            format_out16<GlobalRunsAt, NT>(o0, total, nres, sdec, a0, N, n_hi - n_lo, ntot, L, l_hi - l_lo, out);
+            format_out16(o0, total, nres, sdec, a0, N, n_hi - n_lo, ntot, L, l_hi - l_lo, out);
         }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Pipelined formatter (opt-in, SCCG_FMT_PIPE=1): a resident grid (8 blocks per CU) walks the output tiles of
-// k_format_out, block b taking tiles b, b + G, b + 2G, ...; while it formats one tile from LDS the
-// loads of the next (its decoded words and runs, into registers) and the k_out_index row of the one
-// after are in flight, so a tile costs max(format, memory) instead of two dependent HBM round trips
-// plus the format (k_format_out: 62 k blocks in ~30 generations, ~9 us each for chr1).  Two LDS
-// buffers alternate; tiles touching more than PRUNS runs of a kind read that run list from global.
-// ---------------------------------------------------------------------------------------------
-constexpr int PRUNS = 128;
-
-struct PipeRegs {
-    uint32_t w[5];
-    int32_t ns, ne, ls, le;
-    int64_t nb;
-};
-
-struct PipeTile {
-    int64_t d0, d1, a0, nw, n_lo, n_hi, l_lo, l_hi;
-    bool lds;
-    __device__ PipeTile(const int64_t* r, int64_t nn, int64_t nlr) {
-        d0 = r[0];
-        d1 = r[TW];
-        a0 = d0 & ~(int64_t)3;
-        nw = (d1 - a0 + 3) >> 2;
-        n_lo = r[1];
-        n_hi = r[TW + 1] < nn ? r[TW + 1] + 1 : nn;
-        l_lo = r[2];
-        l_hi = r[TW + 2] < nlr ? r[TW + 2] + 1 : nlr;
-        lds = n_hi - n_lo <= PRUNS && l_hi - l_lo <= PRUNS;
-    }
-};
-
-__device__ __forceinline__ void pipe_load(const PipeTile& T, const uint8_t* __restrict__ dec, const int32_t* __restrict__ ns,
-                                          const int32_t* __restrict__ nl, const int64_t* __restrict__ ncum,
-                                          const int32_t* __restrict__ ls, const int32_t* __restrict__ ll, int tid, PipeRegs& R) {
-    const uint32_t* decw = reinterpret_cast<const uint32_t*>(dec + T.a0);
-#pragma unroll
-    for (int q = 0; q < 5; q++) R.w[q] = tid + 256 * q < T.nw ? decw[tid + 256 * q] : 0u;
-    if (T.lds) {
-        const int64_t rn = T.n_lo + tid, rl = T.l_lo + tid;
-        if (rn < T.n_hi) { R.ns = ns[rn]; R.ne = R.ns + nl[rn]; R.nb = ncum[rn]; }
-        if (rl < T.l_hi) { R.ls = ls[rl]; R.le = R.ls + ll[rl]; }
-    }
-}
-
-__device__ __forceinline__ void pipe_store(const PipeTile& T, const PipeRegs& R, int tid, uint32_t* sdec, int32_t* sns,
-                                           int32_t* sne, int64_t* snb, int32_t* sls, int32_t* sle) {
-#pragma unroll
-    for (int q = 0; q < 5; q++)
-        if (tid + 256 * q < T.nw) sdec[tid + 256 * q] = R.w[q];
-    if (T.lds) {
-        if (T.n_lo + tid < T.n_hi) { sns[tid] = R.ns; sne[tid] = R.ne; snb[tid] = R.nb; }
-        if (T.l_lo + tid < T.l_hi) { sls[tid] = R.ls; sle[tid] = R.le; }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_format_pipe(const uint8_t* __restrict__ dec, int64_t nres, int64_t total, int64_t o_first,
-                                                     int64_t nblk, const int32_t* __restrict__ ns, const int32_t* __restrict__ nl,
-                                                     const int64_t* __restrict__ ncum, int64_t nn,
-                                                     const int32_t* __restrict__ ls, const int32_t* __restrict__ ll,
-                                                     int64_t nlr, const int64_t* __restrict__ tab, uint8_t* __restrict__ out) {
-    static_assert(5 * 256 >= OB / 4 + 2, "five words per thread cover a tile's decoded bytes");
-    __shared__ uint32_t sdec[2][OB / 4 + 4];
-    __shared__ int32_t s_ns[2][PRUNS], s_ne[2][PRUNS], s_ls[2][PRUNS], s_le[2][PRUNS];
-    __shared__ int64_t s_nb[2][PRUNS];
-    __shared__ int64_t st[3][2 * TW];
-    const int tid = threadIdx.x;
-    const int64_t G = gridDim.x, b0 = blockIdx.x;
-    if (b0 >= nblk) return;
-    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
-    if (tid < 2 * TW) {
-        st[0][tid] = tab[TW * b0 + tid];
-        if (b0 + G < nblk) st[1][tid] = tab[TW * (b0 + G) + tid];
-    }
-    __syncthreads();
-    PipeRegs R{};
-    {
-        const PipeTile T(st[0], nn, nlr);
-        pipe_load(T, dec, ns, nl, ncum, ls, ll, tid, R);
-        pipe_store(T, R, tid, sdec[0], s_ns[0], s_ne[0], s_nb[0], s_ls[0], s_le[0]);
-    }
-    __syncthreads();
-    for (int64_t i = 0;; i++) {
-        const int64_t bc = b0 + i * G;
-        if (bc >= nblk) break;
-        const int cur = (int)(i & 1), nxt = cur ^ 1;
-        const bool has_next = bc + G < nblk;
-        // the next tile's loads and the row after it, in flight while this tile is formatted
-        int64_t tv = 0;
-        if (has_next) {
-            const PipeTile Tn(st[(i + 1) % 3], nn, nlr);   // (rebuilt from LDS after the format: fewer live registers)
-            pipe_load(Tn, dec, ns, nl, ncum, ls, ll, tid, R);
-            if (tid < 2 * TW && bc + 2 * G < nblk) tv = tab[TW * (bc + 2 * G) + tid];
-        }
-        {
-            const PipeTile T(st[i % 3], nn, nlr);
-            const uint8_t* sd = reinterpret_cast<const uint8_t*>(sdec[cur]);
-            const int64_t o0 = o_first + bc * OB + (int64_t)tid * OPT;
-            if (T.lds) {
-                const LdsRuns N{s_ns[cur], s_ne[cur], s_nb[cur]}, L{s_ls[cur], s_le[cur], nullptr};
-                format_out16(o0, total, nres, sd, T.a0, N, T.n_hi - T.n_lo, ntot, L, T.l_hi - T.l_lo, out);
-            } else {
-                const GlobalRunsAt N{ns, nl, ncum, T.n_lo}, L{ls, ll, nullptr, T.l_lo};
-                format_out16(o0, total, nres, sd, T.a0, N, T.n_hi - T.n_lo, ntot, L, T.l_hi - T.l_lo, out);
-            }
-        }
-        if (!has_next) break;
-        __syncthreads();   // buffer nxt (tile i - 1's) and row (i + 2) % 3 (= (i - 1) % 3) are free
-        {
-            const PipeTile Tn(st[(i + 1) % 3], nn, nlr);
-            pipe_store(Tn, R, tid, sdec[nxt], s_ns[nxt], s_ne[nxt], s_nb[nxt], s_ls[nxt], s_le[nxt]);
-        }
-        if (tid < 2 * TW) st[(i + 2) % 3][tid] = tv;
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Fused reconstruction formatter (opt-in, SCCG_DC_FUSED=1): k_format_out with the block's decoded bytes expanded
-// from the token table instead of read from a decoded buffer -- the tokens the block touches
-// (k_out_index entries t_b .. t_b+1) are staged in LDS beside its runs, then each thread gathers 16
-// decoded bytes (a token's R' bytes with five dword loads, else bytes from R' / the record's
-// literals) into the block's LDS copy, and formats as k_format_out.  The decoded buffer is never
-// written or re-read (the fill wrote ~|T| bytes and the formatter read them back), and the token
-// table is built beside the reference strip, so the strip is followed directly by this kernel.
-// ---------------------------------------------------------------------------------------------
-constexpr int OTOK = 128;
-
-struct TokLds {
-    const int64_t *o, *p, *l, *r;
-    int64_t base;
-    __device__ int64_t O(int64_t t) const { return o[t - base]; }
-    __device__ int64_t P(int64_t t) const { return p[t - base]; }
-    __device__ int64_t L(int64_t t) const { return l[t - base]; }
-    __device__ int64_t R(int64_t t) const { return r[t - base]; }
-};
-struct TokGlobal {
-    const int64_t *o, *p, *l, *r;
-    __device__ int64_t O(int64_t t) const { return o[t]; }
-    __device__ int64_t P(int64_t t) const { return p[t]; }
-    __device__ int64_t L(int64_t t) const { return l[t]; }
-    __device__ int64_t R(int64_t t) const { return r[t]; }
-};
-
-// decoded bytes [x, x + 16) into w[0..3] (bytes outside [d0, d1) are 0: no format position reads them)
-template <typename TV>
-__device__ __forceinline__ void expand16(int64_t x, int64_t d0, int64_t d1, int64_t t_lo, int64_t t_hi, const TV& T,
-                                         const uint8_t* __restrict__ R, int64_t nref, const uint8_t* __restrict__ rec,
-                                         int64_t nrec, uint32_t* w) {
-    const int64_t xs = x < d0 ? d0 : x;
-    int64_t lo = t_lo, hi = t_hi;   // last entry with o <= xs (o of t_lo <= d0 by construction)
-    while (lo < hi) {
-        const int64_t m = (lo + hi + 1) >> 1;
-        if (T.O(m) <= xs) lo = m; else hi = m - 1;
-    }
-    int64_t t = lo, o = T.O(t), l = T.L(t), p = T.P(t), r = T.R(t);
-    int64_t onext = t < t_hi ? T.O(t + 1) : INT64_MAX;
-    bool pv = p >= 0 && p + l <= nref;
-    if (x >= o && x + 16 <= o + l && pv) {   // all 16 from one token: dword loads (R' has >= 64 B of slack)
-        const uint8_t* s0 = R + p + (x - o);
-        const unsigned sh = (unsigned)((uintptr_t)s0 & 3);
-        const uint32_t* a = reinterpret_cast<const uint32_t*>((uintptr_t)s0 & ~(uintptr_t)3);
-        const uint32_t w0 = a[0], w1 = a[1], w2 = a[2], w3 = a[3], w4 = a[4];
-        w[0] = __builtin_amdgcn_alignbyte(w1, w0, sh);
-        w[1] = __builtin_amdgcn_alignbyte(w2, w1, sh);
-        w[2] = __builtin_amdgcn_alignbyte(w3, w2, sh);
-        w[3] = __builtin_amdgcn_alignbyte(w4, w3, sh);
-        return;
-    }
-    // every source first (a 32-bit code: R' offset, or the record offset | 1 << 31; ~0 = none; the
-    // host takes this path only when |R'| and the record line are below 2^31), then all 16 loads
-    uint32_t src[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int64_t y = x + k;
-        src[k] = ~0u;
-        if (y >= xs && y < d1) {
-            while (y >= onext) {
-                t++;
-                o = onext; l = T.L(t); p = T.P(t); r = T.R(t);
-                onext = t < t_hi ? T.O(t + 1) : INT64_MAX;
-                pv = p >= 0 && p + l <= nref;
-            }
-            if (y < o + l) {
-                if (pv) src[k] = (uint32_t)(p + (y - o));
-            } else {
-                const int64_t q = r + (y - o - l);
-                if (q >= 0 && q < nrec) src[k] = (uint32_t)q | 0x80000000u;
-            }
-        }
-    }
-    uint32_t v[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const uint32_t c = src[k];
-        const uint32_t b = c == ~0u ? 0u : (c >> 31) ? rec[c & 0x7fffffffu] : R[c];
-        v[k >> 2] |= b << (8 * (k & 3));
-    }
-    w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
-}
-
-#ifndef SCCG_FUSED_WAVES
-#define SCCG_FUSED_WAVES 1
-#endif
-__global__ __launch_bounds__(256, SCCG_FUSED_WAVES) void k_format_fused(DcFmtSrc F, int64_t nres, int64_t total, int64_t o_first,
-                                                      const int32_t* __restrict__ ns, const int32_t* __restrict__ nl,
-                                                      const int64_t* __restrict__ ncum, int64_t nn,
-                                                      const int32_t* __restrict__ ls, const int32_t* __restrict__ ll,
-                                                      int64_t nlr, const int64_t* __restrict__ tab, uint8_t* __restrict__ out) {
-    __shared__ uint32_t sdec_w[OB / 4 + 8];
-    __shared__ int32_t s_ns[OFRUNS], s_ne[OFRUNS], s_ls[OFRUNS], s_le[OFRUNS];
-    __shared__ int64_t s_nb[OFRUNS];
-    __shared__ int64_t s_to[OTOK], s_tp[OTOK], s_tl[OTOK], s_tr[OTOK];
-    __shared__ int64_t st[2 * TW + 1];
-    const int tid = threadIdx.x;
-    const int64_t b = blockIdx.x;
-    if (tid < 2 * TW) st[tid] = tab[TW * b + tid];
-    if (tid == 2 * TW) st[2 * TW] = *F.d_nref;
-    __syncthreads();
-    const int64_t d0 = st[0], d1 = st[TW];
-    const int64_t n_lo = st[1], n_hi = st[TW + 1] < nn ? st[TW + 1] + 1 : nn;
-    const int64_t l_lo = st[2], l_hi = st[TW + 2] < nlr ? st[TW + 2] + 1 : nlr;
-    const int64_t t_lo = st[4], t_hi = st[TW + 4];
-    const int64_t nref = st[2 * TW];
-    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
-    const bool lds_runs = n_hi - n_lo <= OFRUNS && l_hi - l_lo <= OFRUNS;
-    const bool lds_tok = t_hi - t_lo < OTOK;
-    if (lds_tok) {
-        for (int64_t t = t_lo + tid; t <= t_hi; t += 256) {
-            s_to[t - t_lo] = F.tk.o[t];
-            s_tp[t - t_lo] = F.tk.p[t];
-            s_tl[t - t_lo] = F.tk.l[t];
-            s_tr[t - t_lo] = F.tk.r[t];
-        }
-    }
-    if (lds_runs) {
-        for (int64_t r = n_lo + tid; r < n_hi; r += 256) {
-            const int32_t x = ns[r];
-            s_ns[r - n_lo] = x;
-            s_ne[r - n_lo] = x + nl[r];
-            s_nb[r - n_lo] = ncum[r];
-        }
-        for (int64_t r = l_lo + tid; r < l_hi; r += 256) {
-            const int32_t x = ls[r];
-            s_ls[r - l_lo] = x;
-            s_le[r - l_lo] = x + ll[r];
-        }
-    }
-    __syncthreads();
-    const int64_t a0 = d0 & ~(int64_t)3;
-    const int64_t nch = (d1 - a0 + 15) >> 4;
-    for (int64_t c = tid; c < nch; c += 256) {
-        uint32_t* w = sdec_w + 4 * c;
-        if (lds_tok) expand16(a0 + 16 * c, d0, d1, t_lo, t_hi, TokLds{s_to, s_tp, s_tl, s_tr, t_lo}, F.R, nref, F.rec, F.nrec, w);
-        else expand16(a0 + 16 * c, d0, d1, t_lo, t_hi, TokGlobal{F.tk.o, F.tk.p, F.tk.l, F.tk.r}, F.R, nref, F.rec, F.nrec, w);
-    }
-    __syncthreads();
-    const uint8_t* sdec = reinterpret_cast<const uint8_t*>(sdec_w);
-    const int64_t o0 = o_first + b * OB + (int64_t)tid * OPT;
-    if (lds_runs) {
-        const LdsRuns N{s_ns, s_ne, s_nb}, L{s_ls, s_le, nullptr};
-        format_out16(o0, total, nres, sdec, a0, N, n_hi - n_lo, ntot, L, l_hi - l_lo, out);
-    } else {
-        const GlobalRunsAt N{ns, nl, ncum, n_lo}, L{ls, ll, nullptr, l_lo};
-        format_out16(o0, total, nres, sdec, a0, N, n_hi - n_lo, ntot, L, l_hi - l_lo, out);
     }
 }
 
@@ -1571,13 +964,9 @@ int dc_last_paren(const uint8_t* d_s, int64_t n, int64_t* d_lp, int64_t* d_parti
 int64_t dc_run_cap(int64_t n) { return n / 2 + 2; }
 
 namespace {
-bool rl_tiled() {   // (SCCG_RL_SCAN=1, A/B runs: the scan-based parser)
-    static const bool v = getenv("SCCG_RL_SCAN") == nullptr;
-    return v;
-}
-bool rl_tiled_ok(int64_t n) { return rl_tiled() && (n + RL_TILE - 1) / RL_TILE <= 64 * 1024; }
+bool rl_tiled_ok(int64_t n) { return (n + RL_TILE - 1) / RL_TILE <= 64 * 1024; }
 
-// the scan-based parser of one line (lines over 64 MiB, or SCCG_RL_SCAN)
+// the scan-based parser of one line (lines of more than 64 Ki tiles)
 int parse_runs_scan(const uint8_t* d_s, int64_t n, DcRuns* r, int64_t* d_lp, int64_t* d_flag, int64_t* d_dlt,
                     int64_t* d_partial, int32_t* d_err, int64_t* d_count, hipStream_t s) {
     if (n <= 0) {
@@ -1652,220 +1041,73 @@ int dc_n_check(const DcRuns& nr, const int64_t* d_ncnt, const int64_t* d_D, int3
 }
 
 int dc_decode_prepare(const uint8_t* d_s, int64_t n, int64_t* d_lp, int64_t* d_contrib, int64_t* d_dlt, int64_t* d_off,
-                      int64_t* d_dsum, const int64_t* d_nref, hipEvent_t nref_ready, int64_t* d_partial, int32_t* d_err,
-                      int64_t* d_total, hipStream_t s, const DcTokBuf* tk) {
+                      int64_t* d_dsum, int64_t* d_partial, int32_t* d_err, int64_t* d_total, hipStream_t s) {
     if (n <= 0) {
         SCCG_HIP(hipMemsetAsync(d_total, 0, sizeof(int64_t), s));
-        if (tk) {   // no tokens: the sentinel entry alone
-            SCCG_HIP(hipMemsetAsync(tk->d_ntok, 0, sizeof(int64_t), s));
-            for (int64_t* a : {tk->tab.o, tk->tab.p, tk->tab.l, tk->tab.r}) SCCG_HIP(hipMemsetAsync(a, 0, sizeof(int64_t), s));
-        }
         return 0;
     }
-    if (dc_tok_tiled()) {
-        // per 64-byte block: state, output bytes, deltas; their exclusive prefixes -> d_off, d_dsum
-        const int64_t nb = (n + TK_B - 1) / TK_B;
-        const unsigned g = (unsigned)((n + 4 * 1024 - 1) / (4 * 1024));   // 4 waves of 1 KiB per block
-        hipLaunchKernelGGL(k_tok_blocks, dim3(g), dim3(256), 0, s, d_s, n, d_lp, d_contrib, d_dlt, d_err,
-                           tk ? tk->btok : nullptr);
-        SCCG_HIP(hipGetLastError());
-        // (d_partial: scan_partials_needed(n + 1) + 16 >= 2 * scan_partials_needed(nb))
-        int rc = dev_excl_sum2(d_contrib, d_off, d_total, d_dlt, d_dsum, nullptr, nb, d_partial, s);
-        if (rc || !tk) return rc;   // (unfused: the range check is in the fill, dc_decode_fill)
-        rc = dev_excl_sum(tk->btok, tk->btoff, nb, tk->d_ntok, d_partial, s);
-        if (rc) return rc;
-        PROF_LAUNCH(PROF_DC_DECODE, s, k_tok_emit, dim3(grid_for(nb, WPB)), dim3(SCCG_BLOCK), 0, s, d_s, n, (const int64_t*)d_lp,
-                    (const int64_t*)d_off, (const int64_t*)d_dsum, (const int64_t*)tk->btoff, tk->tab);
-        SCCG_HIP(hipGetLastError());
-        (void)d_nref;
-        (void)nref_ready;
-        return 0;   // (the range check: dc_tok_range, after the reference strip)
-    }
-    int rc = dc_last_paren(d_s, n, d_lp, d_partial, s);
-    if (rc) return rc;
-    const unsigned g = grid_for(n, 256) > 8192 ? 8192 : grid_for(n, 256);
-    hipLaunchKernelGGL(k_tok_parse, dim3(g), dim3(256), 0, s, d_s, n, (const int64_t*)d_lp, d_contrib, d_dlt, d_err);
+    // per 64-byte block: state, output bytes, deltas; their exclusive prefixes -> d_off, d_dsum
+    const int64_t nb = (n + TK_B - 1) / TK_B;
+    const unsigned g = (unsigned)((n + 4 * 1024 - 1) / (4 * 1024));   // 4 waves of 1 KiB per block
+    hipLaunchKernelGGL(k_tok_blocks, dim3(g), dim3(256), 0, s, d_s, n, d_lp, d_contrib, d_dlt, d_err);
     SCCG_HIP(hipGetLastError());
-    rc = dev_excl_sum(d_contrib, d_off, n, d_total, d_partial, s);
-    if (rc) return rc;
-    rc = dev_excl_sum(d_dlt, d_dsum, n, nullptr, d_partial, s);
-    if (rc) return rc;
-    if (nref_ready) SCCG_HIP(hipStreamWaitEvent(s, nref_ready, 0));
-    hipLaunchKernelGGL(k_tok_check, dim3(g), dim3(256), 0, s, d_s, n, (const int64_t*)d_dsum, (const int64_t*)d_dlt,
-                       (const int64_t*)d_contrib, d_nref, d_err);
-    SCCG_HIP(hipGetLastError());
-    return 0;
-}
-
-int64_t dc_tok_cap(int64_t n) { return n / 5 + 2; }   // a token "(d,l)" takes >= 5 bytes; tokens are disjoint
-
-bool dc_fused() {   // (opt-in, SCCG_DC_FUSED=1: measured slower so far)
-    static const bool v = dc_tok_tiled() && getenv("SCCG_DC_FUSED") != nullptr;
-    return v;
-}
-
-int dc_tok_range(const DcTokBuf& tk, int64_t cap, const int64_t* d_nref, int32_t* d_err, hipStream_t s) {
-    const unsigned g = grid_for(cap, 256) > 1024 ? 1024 : grid_for(cap, 256);
-    hipLaunchKernelGGL(k_tok_range, dim3(g), dim3(256), 0, s, tk.tab, (const int64_t*)tk.d_ntok, d_nref, d_err);
-    SCCG_HIP(hipGetLastError());
-    return 0;
-}
-
-bool dc_tok_tiled() {
-    // (SCCG_TOK_SCAN=1, A/B runs: the scan-based record-line path; chr1 1.04-1.05 ms vs 1.02-1.03 tiled)
-    static const bool v = getenv("SCCG_TOK_SCAN") == nullptr;
-    return v;
+    // (d_partial: scan_partials_needed(n + 1) + 16 >= 2 * scan_partials_needed(nb))
+    return dev_excl_sum2(d_contrib, d_off, d_total, d_dlt, d_dsum, nullptr, nb, d_partial, s);
 }
 
 int dc_decode_fill(const uint8_t* d_s, int64_t n, const int64_t* d_lp, const int64_t* d_off, const int64_t* d_dsum,
-                   const int64_t* d_dlt, const int64_t* d_contrib, const uint8_t* d_R, uint8_t* d_dec, hipStream_t s,
-                   const int64_t* d_nref, int32_t* d_err, int64_t dcap) {
+                   const uint8_t* d_R, uint8_t* d_dec, hipStream_t s, const int64_t* d_nref, int32_t* d_err, int64_t dcap) {
     if (n <= 0) return 0;
-    if (dc_tok_tiled()) {
-        PROF_LAUNCH(PROF_DC_DECODE, s, k_tok_fill2<true>, dim3(grid_for((n + TK_B - 1) / TK_B, WPB)), dim3(SCCG_BLOCK), 0, s, d_s, n,
-                    d_lp, d_off, d_dsum, d_nref, d_R, d_dec, d_err, dcap);
-        SCCG_HIP(hipGetLastError());
-        return 0;
-    }
-    PROF_LAUNCH(PROF_DC_DECODE, s, k_tok_fill, dim3(grid_for(n, 64 * WPB)), dim3(SCCG_BLOCK), 0, s, d_s, n, d_lp, d_off, d_dsum, d_dlt,
-                       d_contrib, d_R, d_dec);
+    PROF_LAUNCH(PROF_DC_DECODE, s, k_tok_fill2<true>, dim3(grid_for((n + TK_B - 1) / TK_B, WPB)), dim3(SCCG_BLOCK), 0, s, d_s, n,
+                d_lp, d_off, d_dsum, d_nref, d_R, d_dec, d_err, dcap);
     SCCG_HIP(hipGetLastError());
     return 0;
 }
 
-int dc_tok_range_tiled(const uint8_t* d_s, int64_t n, const int64_t* d_lp, const int64_t* d_off, const int64_t* d_dsum,
-                       const int64_t* d_nref, int32_t* d_err, hipStream_t s) {
-    if (n <= 0 || !dc_tok_tiled()) return 0;   // (the scan path checked the range in dc_decode_prepare)
+int dc_tok_range(const uint8_t* d_s, int64_t n, const int64_t* d_lp, const int64_t* d_off, const int64_t* d_dsum,
+                 const int64_t* d_nref, int32_t* d_err, hipStream_t s) {
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(k_tok_fill2<false>, dim3(grid_for((n + TK_B - 1) / TK_B, WPB)), dim3(SCCG_BLOCK), 0, s, d_s, n, d_lp,
                        d_off, d_dsum, d_nref, (const uint8_t*)nullptr, (uint8_t*)nullptr, d_err, (int64_t)0);
     SCCG_HIP(hipGetLastError());
     return 0;
 }
 
-int64_t dc_format_span_words(int64_t nres) {   // (both formatters' tables; the output's misalignment adds a block)
-    const int64_t a = 3 * ((nres + FSPAN - 1) / FSPAN + 2), o = TW * ((nres + nres / 50 + 16) / OB + 3);
-    return a > o ? a : o;
-}
+// (one table row per OB output bytes though a block formats FMT_U * OB: the size the workspace has
+// always reserved; the output's misalignment adds a block)
+int64_t dc_format_index_words(int64_t nres) { return TW * ((nres + nres / 50 + 16) / OB + 3); }
 
 namespace {
-bool fmt_span_path() {   // (A/B runs: the position-centric writer)
-    static const bool v = getenv("SCCG_FMT_SPAN") != nullptr;
-    return v;
-}
-bool fmt_pipe() {   // (SCCG_FMT_PIPE=1, A/B runs: the resident pipelined grid)
-    static const bool v = getenv("SCCG_FMT_PIPE") != nullptr;
-    return v;
-}
-int fmt_u() {   // output bytes per k_format_out block: U * OB (the fused and pipelined formatters use OB)
-    static const int v = [] {
-        const char* e = getenv("SCCG_FMT_U");
-        const int u = e ? atoi(e) : FMT_U_DEFAULT;
-        return u == 1 || u == 2 || u == 4 ? u : FMT_U_DEFAULT;
-    }();
-    return v;
-}
 struct FmtGeom {
-    int64_t total, o_first, ob, nblk;
+    int64_t total, o_first, nblk;
 };
-FmtGeom fmt_geom(int64_t nres, const uint8_t* d_out, bool ob1) {
+FmtGeom fmt_geom(int64_t nres, const uint8_t* d_out) {
     FmtGeom g;
     g.total = nres + (nres - 1) / 50;   // the final '\n' is the caller's
     g.o_first = -(int64_t)((uintptr_t)d_out & 15);
-    g.ob = ob1 ? OB : (int64_t)fmt_u() * OB;
-    g.nblk = (g.total - g.o_first + g.ob - 1) / g.ob;
+    g.nblk = (g.total - g.o_first + FMT_U * OB - 1) / (FMT_U * OB);
     return g;
-}
-int launch_out_index(const FmtGeom& g, int64_t nres, const DcRuns& nr, const DcRuns& lr, const DcFmtSrc* fz,
-                     int64_t* d_span, hipStream_t s) {
-    hipLaunchKernelGGL(k_out_index, dim3(grid_for(2 * (g.nblk + 1), 256)), dim3(256), 0, s, nres, g.total, g.o_first, g.nblk,
-                       g.ob, (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
-                       (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, fz ? (const int64_t*)fz->tk.o : nullptr,
-                       fz ? fz->d_ntok : nullptr, d_span);
-    SCCG_HIP(hipGetLastError());
-    return 0;
 }
 }  // namespace
 
-bool dc_format_index(int64_t nres, const DcRuns& nr, const DcRuns& lr, int64_t* d_span, uint8_t* d_out, hipStream_t s,
-                     int* rc) {
-    *rc = 0;
-    if (nres <= 0 || fmt_span_path() || fmt_pipe()) return false;
-    *rc = launch_out_index(fmt_geom(nres, d_out, false), nres, nr, lr, nullptr, d_span, s);
-    return true;
+int dc_format_index(int64_t nres, const DcRuns& nr, const DcRuns& lr, int64_t* d_index, uint8_t* d_out, hipStream_t s) {
+    if (nres <= 0) return 0;
+    const FmtGeom g = fmt_geom(nres, d_out);
+    hipLaunchKernelGGL(k_out_index, dim3(grid_for(2 * (g.nblk + 1), 256)), dim3(256), 0, s, nres, g.total, g.o_first, g.nblk,
+                       (int64_t)FMT_U * OB, (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
+                       (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, d_index);
+    SCCG_HIP(hipGetLastError());
+    return 0;
 }
 
-int dc_format(const uint8_t* d_dec, int64_t nres, const DcRuns& nr, const DcRuns& lr, int64_t* d_span, uint8_t* d_out,
-              hipStream_t s, const DcFmtSrc* fz, hipEvent_t wait_before, bool index_ready) {
-    if (nres <= 0) {
-        if (wait_before) SCCG_HIP(hipStreamWaitEvent(s, wait_before, 0));
-        return 0;
-    }
-    const bool span_path = fmt_span_path();
-    if (fz || !span_path) {
-        static const bool fmt_nt = [] {
-            const char* e = getenv("SCCG_FMT_NT");
-            return e ? atoi(e) != 0 : FMT_NT_DEFAULT;
-        }();
-        const bool pipe = fmt_pipe();
-        const FmtGeom g = fmt_geom(nres, d_out, fz || pipe);
-        const int64_t total = g.total, o_first = g.o_first, nblk = g.nblk;
-        if (!index_ready || fz || pipe) {
-            const int rc = launch_out_index(g, nres, nr, lr, fz, d_span, s);
-            if (rc) return rc;
-        }
-        if (wait_before) SCCG_HIP(hipStreamWaitEvent(s, wait_before, 0));
-        if (fz) {
-            PROF_LAUNCH(PROF_DC_FORMAT, s, k_format_fused, dim3((unsigned)nblk), dim3(256), 0, s, *fz, nres, total, o_first,
-                        (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
-                        (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, (const int64_t*)d_span, d_out);
-            SCCG_HIP(hipGetLastError());
-            return 0;
-        }
-        // (SCCG_FMT_PIPE=1, A/B runs: the resident pipelined grid; measured slower)
-        if (pipe) {
-            static const int cus = [] {
-                int dev = 0, n = 0;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-                return n > 0 ? n : 256;
-            }();
-            // resident blocks only (every block walks the same number of tiles: a second generation
-            // of blocks would double the time)
-            static const int per_cu = [] {
-                const char* e = getenv("SCCG_FMT_PIPE_BPC");
-                if (e && atoi(e) > 0) return atoi(e);
-                int n = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_format_pipe, 256, 0) != hipSuccess || n <= 0) n = 4;
-                return n;
-            }();
-            const int64_t g = (int64_t)cus * per_cu < nblk ? (int64_t)cus * per_cu : nblk;
-            PROF_LAUNCH(PROF_DC_FORMAT, s, k_format_pipe, dim3((unsigned)g), dim3(256), 0, s, d_dec, nres, total, o_first, nblk,
-                        (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
-                        (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, (const int64_t*)d_span, d_out);
-            SCCG_HIP(hipGetLastError());
-            return 0;
-        }
-#define SCCG_FMT_LAUNCH(U, NT)                                                                                       \
-    PROF_LAUNCH(PROF_DC_FORMAT, s, (k_format_out<U, NT>), dim3((unsigned)nblk), dim3(256), 0, s, d_dec, nres, total, o_first, \
-                (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,                          \
-                (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, (const int64_t*)d_span, d_out)
-        const int fu = fmt_u();
-        if (fu == 1) { if (fmt_nt) SCCG_FMT_LAUNCH(1, true); else SCCG_FMT_LAUNCH(1, false); }
-        else if (fu == 2) { if (fmt_nt) SCCG_FMT_LAUNCH(2, true); else SCCG_FMT_LAUNCH(2, false); }
-        else { if (fmt_nt) SCCG_FMT_LAUNCH(4, true); else SCCG_FMT_LAUNCH(4, false); }
-#undef SCCG_FMT_LAUNCH
-        SCCG_HIP(hipGetLastError());
-        return 0;
-    }
+int dc_format(const uint8_t* d_dec, int64_t nres, const DcRuns& nr, const DcRuns& lr, const int64_t* d_index, uint8_t* d_out,
+              hipStream_t s, hipEvent_t wait_before) {
     if (wait_before) SCCG_HIP(hipStreamWaitEvent(s, wait_before, 0));
-    const int64_t nspan = (nres + FSPAN - 1) / FSPAN;
-    hipLaunchKernelGGL(k_span_index, dim3(grid_for(2 * (nspan + 1), 256)), dim3(256), 0, s, nres, nspan,
-                       (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
-                       (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, d_span);
-    SCCG_HIP(hipGetLastError());
-    PROF_LAUNCH(PROF_DC_FORMAT, s, k_format_span, dim3((unsigned)nspan), dim3(256), 0, s, d_dec, nres,
-                       (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
-                       (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, (const int64_t*)d_span, d_out);
+    if (nres <= 0) return 0;
+    const FmtGeom g = fmt_geom(nres, d_out);
+    PROF_LAUNCH(PROF_DC_FORMAT, s, k_format_out, dim3((unsigned)g.nblk), dim3(256), 0, s, d_dec, nres, g.total, g.o_first,
+                (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
+                (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, d_index, d_out);
     SCCG_HIP(hipGetLastError());
     return 0;
 }

@@ -318,37 +318,6 @@ __device__ __forceinline__ StripMasks strip_masks(FilterMode fm, const uint32_t 
     return r;
 }
 
-// A lane's 64 bytes of a wave tile.  Loaded coalesced (SCCG_STRIP_COALESCED, default): load q of the
-// wave reads the tile's q-th KiB, 16 bytes per lane in lane order (8 cache lines per instruction,
-// against 32 when every lane reads its own 64 contiguous bytes), through the wave's 4 KiB of LDS,
-// from which every lane reads back its 64 contiguous bytes.
-#ifndef SCCG_STRIP_COALESCED
-#define SCCG_STRIP_COALESCED 0
-#endif
-__device__ __forceinline__ void load_lane64(const uint8_t* __restrict__ buf, int64_t n, int64_t off, uint4* __restrict__ tin,
-                                            uint32_t (&w)[SNW]) {
-    const int lane = lane_id();
-    const int64_t t0 = off - (int64_t)lane * SL;   // the wave tile's first byte
-    if (SCCG_STRIP_COALESCED && tin && t0 + STRIP_WTILE <= n && (((uintptr_t)(buf + t0)) & 15) == 0) {
-        const uint4* p = reinterpret_cast<const uint4*>(buf + t0);
-        uint4 v[SNW / 4];
-#pragma unroll
-        for (int q = 0; q < SNW / 4; q++) v[q] = p[64 * q + lane];
-        wave_sync();   // (the previous user of tin is done)
-#pragma unroll
-        for (int q = 0; q < SNW / 4; q++) tin[64 * q + lane] = v[q];
-        wave_sync();
-#pragma unroll
-        for (int q = 0; q < SNW / 4; q++) {
-            const uint4 x = tin[4 * lane + q];
-            w[4 * q] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w;
-        }
-        wave_sync();   // tin is free again (k_strip_write stages its output there)
-    } else {
-        load_words<SNW>(buf, n, off, w);
-    }
-}
-
 // A wave's tile: its words, the byte before it (lane 0's 'prev'), the masks, and each lane's prior
 // line status inside the wave (-1: no line start in the lanes before it).
 template <IngestMode MODE, bool RUNS = false, bool ODD = false>
@@ -356,16 +325,12 @@ __device__ __forceinline__ StripMasks strip_tile(FilterMode fm, const uint8_t* _
                                                  int64_t he, int64_t off, uint32_t (&w)[SNW], int32_t& prior,
                                                  uint64_t& lsm, uint4* tin) {
     const int lane = lane_id();
-    load_lane64(buf, n, off, tin, w);
-    // the lane's 64 bytes in the wave's LDS buffer, for strip_masks' byte lookups (the coalesced
-    // load leaves them there already, in the same layout)
-    if (!(SCCG_STRIP_COALESCED && tin && off - (int64_t)lane * SL + STRIP_WTILE <= n &&
-          (((uintptr_t)(buf + off - (int64_t)lane * SL)) & 15) == 0)) {
-        wave_sync();
+    load_words<SNW>(buf, n, off, w);   // every lane its own 64 contiguous bytes
+    // ... and a copy of them in the wave's LDS buffer, for strip_masks' byte lookups
+    wave_sync();
 #pragma unroll
-        for (int q = 0; q < SNW / 4; q++) tin[4 * lane + q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-        wave_sync();
-    }
+    for (int q = 0; q < SNW / 4; q++) tin[4 * lane + q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    wave_sync();
     uint8_t prev = '\n';
     if (MODE == INGEST_REF) {
         const uint32_t up = (uint32_t)__shfl_up((int)w[SNW - 1], 1, 64) >> 24;
@@ -490,13 +455,10 @@ __device__ __forceinline__ TileSum block_scan_tiles(TileSum v, TileSum* wsum, Ti
     return ts_compose(wsum[w], ex);
 }
 
-// (SCCG_SCAN_T threads per block, SCAN_B / SCAN_T tiles per thread.  A 1024-thread block waits for
+// (SCAN_T threads per block, SCAN_B / SCAN_T tiles per thread.  A 1024-thread block waits for
 // a whole free CU -- the target's scan sat ~140 us behind the reference strip's write pass on the
 // side stream in a chr1 trace -- but 256-thread builds measured within noise end to end.)
-#ifndef SCCG_SCAN_T
-#define SCCG_SCAN_T 1024
-#endif
-constexpr int SCAN_T = SCCG_SCAN_T, SCAN_PER = SCAN_B / SCAN_T;
+constexpr int SCAN_T = 1024, SCAN_PER = SCAN_B / SCAN_T;
 __global__ __launch_bounds__(SCAN_T) void k_strip_scan_local(int64_t ntiles, int64_t* __restrict__ ta, int64_t* __restrict__ tb,
                                                           int64_t* __restrict__ tfa, int64_t* __restrict__ tfb,
                                                           int32_t* __restrict__ tlast, TileSum* __restrict__ btot) {

@@ -171,10 +171,7 @@ int launch_local_all(const uint8_t* R, const int64_t* d_nR, const uint8_t* T, co
 // The switch-window probe (local.hip k_local_probe): classes of PROBE_PAIRS segments in runs spread
 // over the pair into pout[0 .. PROBE_PAIRS) (-1 unknown) and their segment indices into
 // pout[PROBE_PAIRS ..); local_probe_window finds the first window among them on the host (-1: none).
-#ifndef SCCG_PROBE_RUNS
-#define SCCG_PROBE_RUNS 16
-#endif
-constexpr int PROBE_PAIRS = SCCG_PROBE_RUNS * 8;
+constexpr int PROBE_PAIRS = 16 * 8;   // (local.hip: PROBE_RUNS runs of PROBE_RUN segments)
 int local_probe_applies(int64_t nseg_max);
 int launch_probe_segs(const int64_t* d_nR, const int64_t* d_nT, int32_t* segs, hipStream_t s);
 int launch_segment_copy(const uint8_t* src, const int64_t* d_len, const int32_t* segs, int nslots, uint8_t* dst,

@@ -575,9 +575,7 @@ __device__ __forceinline__ int32_t seg_count(int64_t nR, int64_t nT) {
     return n >= INT32_MAX / 2 ? 0 : (int32_t)n;   // beyond int positions: the host reports it
 }
 
-#ifndef LOCAL_WAVES_PER_EU
-#define LOCAL_WAVES_PER_EU 4   // the LDS allows 4 waves/SIMD (4 blocks of SegLds x 4); VGPRs must fit 128
-#endif
+constexpr int LOCAL_WAVES_PER_EU = 4;   // the LDS allows 4 waves/SIMD (4 blocks of SegLds x 4); VGPRs must fit 128
 // prove: each segment is first tried by the class-0 proof (seg_prove); a proved segment publishes
 // class 0 without its records (PASS_PROVEN: a pair that stays local computes them afterwards,
 // launch_local_proven) -- only the switch scan of a pair that goes global skips its walk.
@@ -595,8 +593,6 @@ __global__ __launch_bounds__(SCCG_BLOCK) __attribute__((amdgpu_waves_per_eu(LOCA
     const int32_t G = (int32_t)gridDim.x * WPB;
     SegWords cur, nxt;
     int32_t seg = (int32_t)blockIdx.x * WPB + w;
-    // (a probe window already decided the mode: ctl[1] = -1, nothing to start)
-    if (uni(__hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < 0) return;
     if (seg < nseg) seg_words_load(cur, seg, R, nR, T, nT);
     for (; seg < nseg; seg += G) {
         if (seg > uni(__hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) break;
@@ -664,7 +660,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) __attribute__((amdgpu_waves_per_eu(LOCA
 // them decides the pair global and the in-order pass (k_local_all) is never launched; otherwise it
 // runs as before.
 // ---------------------------------------------------------------------------------------------
-constexpr int PROBE_RUN = 8, PROBE_RUNS = SCCG_PROBE_RUNS, PROBE_MIN_SEGS = 512;
+constexpr int PROBE_RUN = 8, PROBE_RUNS = 16, PROBE_MIN_SEGS = 512;
 static_assert(PROBE_RUN * PROBE_RUNS == PROBE_PAIRS, "internal.h's probe size");
 // run r starts at (r + 1) nseg / (RUNS + 1): spread over the pair, clear of its last segments
 // (telomere gaps)
@@ -904,6 +900,12 @@ __global__ void k_copy_upper(const uint8_t* __restrict__ in, int64_t n, uint8_t*
         out[i] = c_toupper(in[i]);
 }
 
+// SCCG_DEBUG (diagnostics, read once): the instrumented kernels and their per-segment clocks
+bool local_debug() {
+    static const bool v = getenv("SCCG_DEBUG") != nullptr;
+    return v;
+}
+
 }  // namespace
 
 int launch_local_pass(int k, int pass, int upper, const uint8_t* R, int64_t nR, const uint8_t* T, int64_t nT, int64_t seg0,
@@ -911,7 +913,7 @@ int launch_local_pass(int k, int pass, int upper, const uint8_t* R, int64_t nR, 
     if (seg_end <= seg0) return 0;
     unsigned g = grid_for(seg_end - seg0, WPB);
     if (g > 4096) g = 4096;
-    static const bool dbg = getenv("SCCG_DEBUG") != nullptr;
+    const bool dbg = local_debug();
     if (dbg) {
         const unsigned long long z[16] = {};
         SCCG_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_local_dbg), z, sizeof z, 0, hipMemcpyHostToDevice, s));
@@ -963,8 +965,7 @@ int launch_local_proven(const uint8_t* R, int64_t nR, const uint8_t* T, int64_t 
 }
 
 int local_probe_applies(int64_t nseg_max) {
-    static const bool probe_on = [] { const char* e = getenv("SCCG_SWITCH_PROBE"); return !e || atoi(e) != 0; }();
-    return probe_on && nseg_max >= PROBE_MIN_SEGS;
+    return nseg_max >= PROBE_MIN_SEGS;
 }
 
 int local_probe_window(const int32_t* pout) {
@@ -1006,7 +1007,7 @@ int launch_probe_segs(const int64_t* d_nR, const int64_t* d_nT, int32_t* segs, h
 
 int launch_local_probe(const uint8_t* gR, const int64_t* d_nR, const uint8_t* gT, const int64_t* d_nT, const int32_t* segs,
                        int32_t* pout, hipStream_t s) {
-    static const bool pdbg = getenv("SCCG_DEBUG") != nullptr;
+    const bool pdbg = local_debug();
     constexpr int NP = PROBE_RUNS * PROBE_RUN;
     if (!pdbg) {
         PROF_LAUNCH(PROF_LOCAL14, s, k_local_probe<false>, dim3(NP), dim3(64), 0, s, gR, d_nR, gT, d_nT, segs, pout);
@@ -1045,15 +1046,13 @@ int launch_local_all(const uint8_t* R, const int64_t* d_nR, const uint8_t* T, co
         // Measured (blocks/CU 4 / 3 / 2): whole genome on 1 GPU 28.5 / 27.3 / 27.2 ms, chr1 pair
         // 1.57 / 1.55 / 1.54 ms, local-mode pair 2.84 / 2.90 / 2.97 ms.  Round 3, genome with two
         // contexts (3 / 2, interleaved, 8 pairs of runs, profiles/r03/local_bpc_ab*): 2 faster in 6 of
-        // 8, medians 22.5-24.1 vs 22.3-22.4 ms -- 2 is the default.  SCCG_LOCAL_BPC overrides.
-        const char* e = getenv("SCCG_LOCAL_BPC");
-        const int bpc = e ? atoi(e) : 2;
-        if (bpc >= 1 && bpc < per) per = bpc;
+        // 8, medians 22.5-24.1 vs 22.3-22.4 ms -- so 2.
+        if (per > 2) per = 2;
         return (unsigned)(cus * per);
     }();
     unsigned g = grid_for(nseg_max, WPB);
     if (g > cap) g = cap;
-    static const bool dbg = getenv("SCCG_DEBUG") != nullptr;
+    const bool dbg = local_debug();
     if (dbg) {
         const unsigned long long z[16] = {};
         SCCG_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_local_dbg), z, sizeof z, 0, hipMemcpyHostToDevice, s));

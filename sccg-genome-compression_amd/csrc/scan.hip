@@ -78,12 +78,9 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_tile_reduce(ScanArrays a, int64_
     if (threadIdx.x == 0) a.partial[blockIdx.y][blockIdx.x] = tot;
 }
 
-// Single-block scans: SCCG_SB_T threads (256-thread builds do not wait for a whole free CU beside
+// Single-block scans: SB_T threads (256-thread builds do not wait for a whole free CU beside
 // other grids; A/B on the genome bench within noise, so 1024 stays).
-#ifndef SCCG_SB_T
-#define SCCG_SB_T 1024
-#endif
-constexpr int SB_T = SCCG_SB_T, PART_PER = 4;
+constexpr int SB_T = 1024, PART_PER = 4;
 // A short scan (the usual case: a few dozen tile partials, or a few thousand elements) runs in one
 // wave or a 256-thread block instead: a 1024-thread block needs a CU with 16 free wave slots, and
 // beside another grid (the reconstruction's reference strip) it waited for one -- 72 us of the chr1

@@ -49,15 +49,14 @@ enum Slot {
     B_SCAL, B_PARTIAL,
     B_RUN_S, B_RUN_E, B_TMP64, B_RUN_SN, B_RUN_EN, B_TMP64N, B_NLINE, B_RECS, B_STAT, B_SEGCLS, B_SEG_A, B_SEG_B, B_RP, B_TP, B_WALK, B_OUT,
     // decompression
-    B_D_LP, B_D_FLAG, B_D_DLT, B_D_CONTRIB, B_D_OFF, B_D_DSUM, B_D_LS, B_D_LL, B_D_LC, B_D_NS, B_D_NL, B_D_NC, B_D_DEC, B_D_SPAN, B_D_NLPOS, B_D_LP2, B_D_DLT2, B_PARTIAL2,
+    B_D_LP, B_D_FLAG, B_D_DLT, B_D_CONTRIB, B_D_OFF, B_D_DSUM, B_D_LS, B_D_LL, B_D_LC, B_D_NS, B_D_NL, B_D_NC, B_D_DEC, B_D_FIDX, B_D_NLPOS, B_D_LP2, B_D_DLT2, B_PARTIAL2,
     // delta_encode's own token scan (targets holding '(')
     B_DX, B_DELTA,
     // a second FASTA-strip scratch set (the reference strips beside the target, on the side stream)
     B_TILE2_A, B_TILE2_B, B_TILE2_FA, B_TILE2_FB, B_TILE2_LAST, B_TILE2_OFF, B_TILE2_OFF2, B_TILE2_CARRY, B_TILE2_BSUM,
-    // fused reconstruction: token table, tokens per record block and their prefix
-    B_D_TOK, B_D_BTOK,
     // the target strip's run-event slots (RunSlots) and the run arrays' per-tile scratch
-    B_RSLOT, B_RTILE,
+    // (slots 60 and 61 are unused: tests/test_gpu_oom.py addresses B_RSLOT by its number)
+    B_RSLOT = 62, B_RTILE,
     B_COUNT
 };
 // (the slot numbers tests/test_gpu_oom.py passes in SCCG_TEST_OOM)
@@ -76,11 +75,8 @@ int walk_chunk(int64_t target_bytes) {
         return c >= 1024 && c <= (1 << 20) ? c : 0;
     }();
     if (env) return env;
-    // (tuning runs: SCCG_WALK_CHUNKS_TARGET / SCCG_WALK_CHUNK_MAX move the size rule)
-    static const int64_t target = [] { const char* e = getenv("SCCG_WALK_CHUNKS_TARGET"); const int64_t v = e ? atoll(e) : 0; return v >= 256 ? v : WALK_CHUNKS_TARGET; }();
-    static const int64_t cmax = [] { const char* e = getenv("SCCG_WALK_CHUNK_MAX"); const int64_t v = e ? atoll(e) : 0; return v >= WALK_CHUNK_MIN && v <= (1 << 20) ? v : (int64_t)WALK_CHUNK_MAX; }();
-    const int64_t c = (target_bytes / target) & ~int64_t(4095);
-    return (int)(c < WALK_CHUNK_MIN ? WALK_CHUNK_MIN : c > cmax ? cmax : c);
+    const int64_t c = (target_bytes / WALK_CHUNKS_TARGET) & ~int64_t(4095);
+    return (int)(c < WALK_CHUNK_MIN ? WALK_CHUNK_MIN : c > WALK_CHUNK_MAX ? WALK_CHUNK_MAX : c);
 }
 constexpr int DPAD = 4096;   // readable slack after every byte buffer (wide compares, tails)
 
@@ -244,13 +240,12 @@ int sccg_ctx_create(int device, sccg_ctx** out) {
     if (hipSetDevice(device) != hipSuccess) return SCCG_E_HIP;
     sccg_ctx* c = new sccg_ctx();
     c->device = device;
-    // the side stream carries the global walk's critical path (R' sweep -> walk rounds -> text):
-    // SCCG_SIDE_PRIORITY=1 (tuning runs) gives it the device's highest stream priority
+    // the side stream carries the global walk's critical path (R' sweep -> walk rounds -> text), at
+    // the device's lowest stream priority
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    static const bool side_prio = [] { const char* e = getenv("SCCG_SIDE_PRIORITY"); return e && atoi(e) > 0; }();
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, side_prio ? prio_hi : prio_lo) != hipSuccess ||
+        hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, prio_lo) != hipSuccess ||
         hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork2, hipEventDisableTiming) != hipSuccess ||
@@ -516,9 +511,8 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
     // R'; the probe gathers its segments of T and R from the FASTA (k_strip_gather), and a pair it
     // leaves local gets T and R from a second write pass (launch_strip_rewrite) before its pass.
     const int64_t iters_max = ((rn < tn ? rn : tn) + SEG_L - 1) / SEG_L;   // FASTA lengths bound the sequences'
-    static const bool lean_on = [] { const char* e = getenv("SCCG_LEAN_STRIP"); return !e || atoi(e) != 0; }();
     const bool probe_mode = !force_global && !ctx->exact_switch && iters_max > 0 && local_probe_applies(iters_max);
-    const bool lean_R = lean_on && (probe_mode || force_global);
+    const bool lean_R = probe_mode || force_global;
     int32_t* d_flags = reinterpret_cast<int32_t*>(sc + 32);
     HIPTRY(hipMemsetAsync(d_flags, 0, sizeof(int32_t), s));
     // local pass control {0, early-exit bound, switch segment, 0}: INT32_MAX = none yet
@@ -647,12 +641,9 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
     uint8_t* probe_gT = reinterpret_cast<uint8_t*>(probe_segs + PROBE_PAIRS);
     uint8_t* probe_gR = probe_gT + PROBE_PAIRS * SEG_GATHER_B;
     int32_t* ctl = reinterpret_cast<int32_t*>(sc + 20);   // {0, bound, switch, 0}
-    // Where the local pass goes.  It fills every CU while it runs (LDS and VGPRs), but only the final
-    // record text needs it; the global walk (side stream) is the critical path of a switching pair.
-    //   0: right after both strips (beside the R' sweep);  1: behind the walk's preparation (the
-    //   first-step statistics);  2: behind walk round 1 (SCCG_LOCAL_ORDER, tuning runs)
-    static const int local_order = [] { const char* e = getenv("SCCG_LOCAL_ORDER"); const int v = e ? atoi(e) : 0; return v >= 0 && v <= 2 ? v : 0; }();
-    bool local_launched = false;
+    // The local pass goes right after both strips, beside the R' sweep.  It fills every CU while it
+    // runs (LDS and VGPRs), but only the final record text needs it; the global walk (side stream) is
+    // the critical path of a switching pair.
     // The switch probe (default; not with SCCG_OPT_EXACT_SWITCH): a few runs of segments spread over
     // the pair are classified first (local.hip k_local_probe); one complete switch window among them
     // decides the pair global (a switching pair's record file does not depend on where it switched,
@@ -672,42 +663,26 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
         TRY(launch_local_all(R, sc + 7, T, sc + 2, iters_max, recs, stat, cls, gen, ctl, s));
         return 0;
     };
-    auto launch_local = [&](hipStream_t after) -> int {
-        if (local_launched) return 0;
-        local_launched = true;
-        if (after) {
-            HIPTRY(hipEventRecord(ctx->ev_fork2, after));
-            HIPTRY(hipStreamWaitEvent(s, ctx->ev_fork2, 0));
+    if (probe_mode) {   // (implies iters_max > 0, a local pass, and R' alone from the reference strip)
+        // the probed segments of T and R, from the FASTA where the strips did not write them
+        TRY(launch_probe_segs(sc + 7, sc + 2, probe_segs, s));
+        if (lean_T) {
+            TRY(launch_strip_gather(INGEST_TGT, tfa, tn, sc, reinterpret_cast<const int64_t*>(ctx->buf[B_TILE_OFF]),
+                                    reinterpret_cast<const int32_t*>(ctx->buf[B_TILE_CARRY]), sc + 2, probe_segs,
+                                    PROBE_PAIRS, probe_gT, s));
+        } else {
+            TRY(launch_segment_copy(T, sc + 2, probe_segs, PROBE_PAIRS, probe_gT, s));
         }
-        if (iters_max > 0 && !force_global) {
-            if (probe_mode) {
-                // the probed segments of T and R, from the FASTA when the strips did not write them
-                TRY(launch_probe_segs(sc + 7, sc + 2, probe_segs, s));
-                if (lean_T) {
-                    TRY(launch_strip_gather(INGEST_TGT, tfa, tn, sc, reinterpret_cast<const int64_t*>(ctx->buf[B_TILE_OFF]),
-                                            reinterpret_cast<const int32_t*>(ctx->buf[B_TILE_CARRY]), sc + 2, probe_segs,
-                                            PROBE_PAIRS, probe_gT, s));
-                } else {
-                    TRY(launch_segment_copy(T, sc + 2, probe_segs, PROBE_PAIRS, probe_gT, s));
-                }
-                if (lean_R) {
-                    TRY(launch_strip_gather(INGEST_REF, rfa, rn, nullptr, reinterpret_cast<const int64_t*>(ctx->buf[B_TILE2_OFF]),
-                                            reinterpret_cast<const int32_t*>(ctx->buf[B_TILE2_CARRY]), sc + 7, probe_segs,
-                                            PROBE_PAIRS, probe_gR, s));
-                } else {
-                    TRY(launch_segment_copy(R, sc + 7, probe_segs, PROBE_PAIRS, probe_gR, s));
-                }
-                TRY(launch_local_probe(probe_gR, sc + 7, probe_gT, sc + 2, probe_segs, probe_out, s));
-                HIPTRY(hipMemcpyAsync(ctx->h_probe, probe_out, 2 * PROBE_PAIRS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                HIPTRY(hipEventRecord(ctx->ev_probe, s));
-                probe_pending = true;
-            } else {
-                TRY(launch_inorder());
-            }
-        }
-        return 0;
-    };
-    if (local_order == 0) TRY(launch_local(nullptr));
+        TRY(launch_strip_gather(INGEST_REF, rfa, rn, nullptr, reinterpret_cast<const int64_t*>(ctx->buf[B_TILE2_OFF]),
+                                reinterpret_cast<const int32_t*>(ctx->buf[B_TILE2_CARRY]), sc + 7, probe_segs,
+                                PROBE_PAIRS, probe_gR, s));
+        TRY(launch_local_probe(probe_gR, sc + 7, probe_gT, sc + 2, probe_segs, probe_out, s));
+        HIPTRY(hipMemcpyAsync(ctx->h_probe, probe_out, 2 * PROBE_PAIRS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPTRY(hipEventRecord(ctx->ev_probe, s));
+        probe_pending = true;
+    } else if (iters_max > 0 && !force_global) {
+        TRY(launch_inorder());
+    }
     TRY(lens.get());
     const int64_t hdr[2] = {h4[0], h4[1]}, lt[2] = {h4[2], h4[3]};
     const int64_t nT = lt[0], nR = lr[0];
@@ -734,7 +709,6 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
     if (!ws) return ctx->fail(SCCG_E_NOMEM, "walk workspace of %zu bytes", wsb);
     TRY(global_prepare(Rp, np[1], Tp, np[0], kg, mg, walk_chunk(tn), ws, wsb, s2));
     HIPTRY(hipEventRecord(ctx->ev_join, s2));
-    if (local_order == 1 || iters <= 0 || force_global) TRY(launch_local(s2));
 
     int64_t pos = 0;
     auto join_lines = [&](hipStream_t on) -> int {   // the lowercase line's end, `on` ordered after it
@@ -777,12 +751,7 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
         sw_known = true;
         return 0;
     };
-    if (local_launched && !probe_pending) TRY(local_tail());
-    auto ensure_local = [&](hipStream_t after) -> int {   // (order 2 when the walk never queued round 1)
-        if (local_launched) return 0;
-        TRY(launch_local(after));
-        return probe_pending ? 0 : local_tail();
-    };
+    if (!probe_pending) TRY(local_tail());
 
     // ---- global (compression.cpp:484-574), speculatively: the walk runs on the side stream right
     //      behind its preparation, beside the local pass, and is abandoned if the pass finds no
@@ -800,7 +769,6 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
             std::function<int(hipStream_t)> r1;
             static int round1(void* u, hipStream_t st) { return static_cast<Late*>(u)->r1(st); }
         } late{[&](uint8_t** o) -> int {
-                   TRY(ensure_local(s2));
                    TRY(read_switch());
                    if (sw < 0 && !force_global) return WALK_ABANDONED;
                    TRY(join_lines(s2));
@@ -816,16 +784,15 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
                    return 0;
                },
                [&]() -> int {
-                   if (force_global || !local_launched) return 0;
+                   if (force_global) return 0;
                    if (decide_probe()) return 0;   // (the resolve step reports the error)
                    if (!sw_known && hipEventQuery(ctx->ev_local) != hipSuccess) return 0;   // pass still running
                    if (read_switch()) return 0;   // the resolve step reports the error
                    return sw < 0;
                },
-               [&](hipStream_t st) -> int {
+               [&](hipStream_t) -> int {
                    // (the probe's verdict once the walk's first rounds are queued: the in-order pass,
                    // when needed, then runs beside them)
-                   TRY(local_order == 2 ? ensure_local(st) : 0);
                    return decide_probe();
                }};
         const EmitTarget target{&Late::call, &late, &Late::abandon, &Late::round1};
@@ -837,7 +804,6 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
             global_done = true;
         }
     }
-    TRY(ensure_local(s2));
     HIPTRY(hipEventRecord(ctx->ev_join, s2));   // all side work (preparation, walk) before anything reuses it
     HIPTRY(hipStreamWaitEvent(s, ctx->ev_join, 0));
     TRY(read_switch());
@@ -1213,19 +1179,6 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     GET(int32_t, ns, B_D_NS, dc_run_cap(nnl));
     GET(int32_t, nlr, B_D_NL, dc_run_cap(nnl));
     GET(int64_t, nc, B_D_NC, dc_run_cap(nnl));
-    // fused path: the record line becomes a token table (no R' needed) that the formatter expands
-    const bool fused = dc_fused() && rn < ((int64_t)1 << 31) && nenc < ((int64_t)1 << 31);   // (32-bit sources)
-    DcTokBuf tk{};
-    const int64_t tcap = dc_tok_cap(nenc > 0 ? nenc : 0);
-    if (fused) {
-        GET(int64_t, tkb, B_D_TOK, 4 * tcap);
-        tk.tab = DcTokTab{tkb, tkb + tcap, tkb + 2 * tcap, tkb + 3 * tcap};
-        const int64_t nbk = (nenc > 0 ? nenc : 0) / 64 + 2;
-        GET(int64_t, btk, B_D_BTOK, 2 * nbk);
-        tk.btok = btk;
-        tk.btoff = btk + nbk;
-        tk.d_ntok = sc + 24;
-    }
     HIPTRY(hipEventRecord(ctx->ev_fork2, s));
     HIPTRY(hipStreamWaitEvent(ctx->side2, ctx->ev_fork2, 0));
     // The host issues launches one at a time, so the chain issued first starts ~40 us earlier.
@@ -1242,8 +1195,7 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
         TRY(dc_parse_runs2(lower, nlower, &lr, sc + 14, nline, nnl, &nr, sc + 16, lp, flag, dlt, part, d_err, ctx->side2));
         HIPTRY(hipEventRecord(ctx->ev_lines, ctx->side2));
     }
-    TRY(dc_decode_prepare(enc, nenc, lp2, contrib, dlt2, doff, dsum, sc + 9, ctx->ev_rstrip, part2, d_err, sc + 12,
-                          s, fused ? &tk : nullptr));
+    TRY(dc_decode_prepare(enc, nenc, lp2, contrib, dlt2, doff, dsum, part2, d_err, sc + 12, s));
     if (!runs_first) {
         TRY(dc_parse_runs2(lower, nlower, &lr, sc + 14, nline, nnl, &nr, sc + 16, lp, flag, dlt, part, d_err, ctx->side2));
         HIPTRY(hipEventRecord(ctx->ev_lines, ctx->side2));
@@ -1261,7 +1213,7 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     // larger output buffer than the record can need (D rarely exceeds |R| + |rec|: every token
     // copies reference bytes, every literal is a record byte) takes the non-speculative path, which
     // sizes it by D; so does a call whose speculative allocation fails.
-    bool spec_fill = spec_on && !fused && dc_tok_tiled() && !size_only && nenc > 0 && out_cap > 0 &&
+    bool spec_fill = spec_on && !size_only && nenc > 0 && out_cap > 0 &&
                      out_cap <= SPEC_FILL_MAX && out_cap <= 2 * (rn + n) + ((int64_t)64 << 20);
     uint8_t* dec_spec = nullptr;
     if (spec_fill) {
@@ -1270,20 +1222,20 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     }
     // (the strip's wait goes ahead of the N check, so nothing but the fork's event sits between the
     // check and the fill; the strip has long finished by then on genome-sized records)
-    if (!dc_tok_tiled() || spec_fill) HIPTRY(hipStreamWaitEvent(s, ctx->ev_rstrip, 0));
+    if (spec_fill) HIPTRY(hipStreamWaitEvent(s, ctx->ev_rstrip, 0));
     TRY(dc_n_check(nr, sc + 16, sc + 12, d_err, s));
     uint8_t* dec = nullptr;
     hipStream_t rbs = s;
     if (spec_fill) {
         dec = dec_spec;
         HIPTRY(hipEventRecord(ctx->ev_fork2, s));
-        TRY(dc_decode_fill(enc, nenc, lp2, doff, dsum, dlt2, contrib, Rp, dec, s, sc + 9, d_err, out_cap));
+        TRY(dc_decode_fill(enc, nenc, lp2, doff, dsum, Rp, dec, s, sc + 9, d_err, out_cap));
         HIPTRY(hipStreamWaitEvent(ctx->side2, ctx->ev_fork2, 0));
         rbs = ctx->side2;
     }
-    // one readback: decoded length, error bits, both run lines' counts and totals -- with the tiled
-    // record line (range check in the fill) it does not wait for the reference's strip, whose |R'|
-    // is read with the final error bits
+    // one readback: decoded length, error bits, both run lines' counts and totals -- the range check
+    // is in the fill, so it does not wait for the reference's strip, whose |R'| is read with the
+    // final error bits
     int64_t D = 0, nRp = 0, cnt[4] = {0, 0, 0, 0};
     int32_t err = 0;
     {
@@ -1297,12 +1249,12 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     const int64_t nres = D + nr.total;
     const int64_t hlen = has_hdr ? end[0] : 0;
     const int64_t total = hlen + 1 + nres + (nres > 0 ? (nres - 1) / 50 : 0) + 1;
-    if (!fused && dc_tok_tiled() && (size_only || (err & 4) || total > out_cap)) {
-        // the tiled record line checks the token range in its fill: a size query or an early error
+    if (size_only || (err & 4) || total > out_cap) {
+        // the record line checks the token range in its fill: a size query or an early error
         // runs that check alone first, so it reports SCCG_E_RANGE as the full decode (and the
         // reference, which exits at :223-229 before it places N) would
         HIPTRY(hipStreamWaitEvent(s, ctx->ev_rstrip, 0));
-        TRY(dc_tok_range_tiled(enc, nenc, lp2, doff, dsum, sc + 9, d_err, s));
+        TRY(dc_tok_range(enc, nenc, lp2, doff, dsum, sc + 9, d_err, s));
         const RbItem it{d_err, &err, (int)sizeof err};
         TRY(dev_readback(&it, 1, s));
         if (err & 2) return ctx->fail(SCCG_E_RANGE, "token exceeds the reference (decompression.cpp:223-229)");
@@ -1311,43 +1263,22 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     *out_len = total;
     if (size_only) return SCCG_OK;
     if (total > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %lld bytes", (long long)total);
-    if (fused) {
-        // range check after the strip on side2; the formatter expands the tokens straight from R'
-        HIPTRY(hipStreamWaitEvent(ctx->side2, ctx->ev_rstrip, 0));
-        TRY(dc_tok_range(tk, tcap, sc + 9, d_err, ctx->side2));
-        HIPTRY(hipEventRecord(ctx->ev_lines, ctx->side2));
-        if (hlen) HIPTRY(hipMemcpyAsync(out, rec, (size_t)hlen, hipMemcpyDeviceToDevice, s));
-        TRY(dev_put_bytes(out + hlen, "\n", 1, s));
-        GET(int64_t, span, B_D_SPAN, dc_format_span_words(nres));
-        const DcFmtSrc fz{tk.tab, tk.d_ntok, enc, nenc > 0 ? nenc : 0, Rp, sc + 9};
-        TRY(dc_format(nullptr, nres, nr, lr, span, out + hlen + 1, s, &fz, ctx->ev_rstrip));
-        TRY(dev_put_bytes(out + total - 1, "\n", 1, s));
-        HIPTRY(hipStreamWaitEvent(s, ctx->ev_lines, 0));
-        const RbItem it[2] = {{d_err, &err, (int)sizeof err}, {sc + 9, &nRp, (int)sizeof nRp}};
-        TRY(dev_readback(it, 2, s));
-        if (err & 2) return ctx->fail(SCCG_E_RANGE, "token exceeds the reference (decompression.cpp:223-229)");
-        ctx->stats.target_bases = nres;
-        ctx->stats.reference_bases = nRp;
-        return SCCG_OK;
-    }
     if (!spec_fill) {   // (the fill is launched first: it is the critical path)
         GET(uint8_t, dec1, B_D_DEC, D + 64);
         dec = dec1;
         HIPTRY(hipEventRecord(ctx->ev_fork2, s));
         HIPTRY(hipStreamWaitEvent(s, ctx->ev_rstrip, 0));   // the fill copies from R'
-        TRY(dc_decode_fill(enc, nenc, lp2, doff, dsum, dlt2, contrib, Rp, dec, s, sc + 9, d_err));
+        TRY(dc_decode_fill(enc, nenc, lp2, doff, dsum, Rp, dec, s, sc + 9, d_err));
         HIPTRY(hipStreamWaitEvent(ctx->side2, ctx->ev_fork2, 0));
     }
-    GET(int64_t, span, B_D_SPAN, dc_format_span_words(nres));
+    GET(int64_t, fidx, B_D_FIDX, dc_format_index_words(nres));
     // side2, beside the token fill: the output's frame (header, its '\n', the final '\n' -- bytes
     // the formatter does not write) and the formatter's block index (run lists only)
     TRY(dev_put_frame(out, rec, hlen, total, ctx->side2));
-    int irc = 0;
-    const bool index_ready = dc_format_index(nres, nr, lr, span, out + hlen + 1, ctx->side2, &irc);
-    TRY(irc);
+    TRY(dc_format_index(nres, nr, lr, fidx, out + hlen + 1, ctx->side2));
     HIPTRY(hipEventRecord(ctx->ev_lines, ctx->side2));
-    TRY(dc_format(dec, nres, nr, lr, span, out + hlen + 1, s, nullptr, ctx->ev_lines, index_ready));
-    {   // (tiled record line: the range check ran with the fill) error bits and |R'| behind the output
+    TRY(dc_format(dec, nres, nr, lr, fidx, out + hlen + 1, s, ctx->ev_lines));
+    {   // (the range check ran with the fill) error bits and |R'| behind the output
         const RbItem it[2] = {{d_err, &err, (int)sizeof err}, {sc + 9, &nRp, (int)sizeof nRp}};
         TRY(dev_readback(it, 2, s));
         if (err & 2) return ctx->fail(SCCG_E_RANGE, "token exceeds the reference (decompression.cpp:223-229)");

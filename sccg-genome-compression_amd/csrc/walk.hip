@@ -30,12 +30,9 @@
 namespace {
 
 constexpr int WPB = 4;                 // chunks (waves) per block
-// k_walk's waves per block (SCCG_WALK_WPB for A/B builds): a block's LDS is released only when all
-// its waves are done, so fewer waves per block let the dispatcher start the next chunk sooner
-#ifndef SCCG_WALK_WPB
-#define SCCG_WALK_WPB 4
-#endif
-constexpr int WWPB = SCCG_WALK_WPB;
+// k_walk's waves per block: a block's LDS is released only when all its waves are done, so fewer
+// waves per block let the dispatcher start the next chunk sooner
+constexpr int WWPB = 4;
 constexpr int WCAP = 256;              // window positions held in LDS (2m+1 <= WCAP)
 constexpr int32_t INVALID = INT32_MIN;
 constexpr int32_t NEVER = INT32_MIN + 1;   // usedX of a chunk never walked: differs from every state
@@ -47,16 +44,14 @@ constexpr int ANCHOR_K = 32;
 constexpr int KEY_K = 15;
 constexpr int KMAX = 32;              // largest k the walk takes
 constexpr int KB_COUNT = 32;          // kb: the first k bytes of T' at [0, k), their count at [32, 36)
-// Reference sample stride (SCCG_ANCHOR_STEP for tuning runs).  Round 5: 64 instead of 32 -- half the
-// table's scattered 8-byte writes (the early sweep's dominant cost: genome bench 4.0-4.4 -> 2.0 ms
-// of sweep per step, gpurun_out/r05r) and no loss in the walk's speculation (hg genome walk and
-// rounds unchanged; a 256-position vote window still holds ~4 samples of an aligned stretch).
-constexpr int ANCHOR_STEP_DEFAULT = 64;
-constexpr int ANCHOR_LOAD_DEFAULT = 1;    // table slots per sample, rounded up to a power of two (SCCG_ANCHOR_LOAD):
+// Reference sample stride.  Round 5: 64 instead of 32 -- half the table's scattered 8-byte writes
+// (the early sweep's dominant cost: genome bench 4.0-4.4 -> 2.0 ms of sweep per step) and no loss
+// in the walk's speculation (hg genome walk and rounds unchanged; a 256-position vote window still
+// holds ~4 samples of an aligned stretch).  The first-step sweep stores the samples (k_key0<true>).
+constexpr int ANCHOR_STEP = 64;
+constexpr int ANCHOR_LOAD = 1;            // table slots per sample, rounded up to a power of two:
                                           // a 64 MiB table for chr1 stays in the MALL (4 slots/sample: 256 MiB, sweep +40 %)
-#ifndef ANCHOR_PROBE_BATCHES
-#define ANCHOR_PROBE_BATCHES 2            // 64 target probes per batch per anchor vote (measured: 2 beats 4)
-#endif
+constexpr int ANCHOR_PROBE_BATCHES = 2;   // 64 target probes per batch per anchor vote (measured: 2 beats 4)
 constexpr uint32_t A_MULTI = 0xFFFFFFFFu;    // anchor position of a 32-mer seen more than once
 constexpr int ANCHOR_RETRIES = 8;             // later votes for a chunk whose start has none
 constexpr int32_t ANCHOR_RETRY_STEP = 512;    // target bases between them
@@ -65,11 +60,7 @@ constexpr int FROZEN_MAX = 256;        // frozen chunks handled per batch (grid.
 constexpr int FROZEN_FIRST = 16;       // the batch launched blind, before the round's sync
 
 enum ChunkKind : int32_t { KIND_SPEC = 0, KIND_FIX = 1, KIND_RESUME = 2 };
-enum ChunkStatus : int32_t { ST_OK = 0, ST_ESC = 1, ST_CONV = 3, ST_DONE = 4, ST_TRUNC = 5 };
-// A fix-up whose predecessor is re-walked in the same round starts from a stale entry: its result
-// counts only if it converges, so it gives up after this many target positions without converging
-// (a stale entry is often garbage, whose walk is a chunk-long stuck literal scan).
-constexpr int32_t STALE_BUDGET_DEFAULT = 0;   // 0: off (SCCG_STALE_BUDGET sets it for tuning runs)
+enum ChunkStatus : int32_t { ST_OK = 0, ST_ESC = 1, ST_CONV = 3, ST_DONE = 4 };
 // A speculative walk that has gone RESEED_GAP target positions without a match re-seeds P from a
 // fresh anchor vote at its position: a bad start guess otherwise leaves it stuck in a chunk-long
 // literal scan.  The trajectory is then a walk from a different state after the re-seed, so a
@@ -83,47 +74,25 @@ constexpr int32_t RESEED_GAP = 1024;
 constexpr int32_t TRAP_P = 4096;
 constexpr int RESPEC_AHEAD = 256;
 constexpr int RESPEC_MAX_TRIGGERS = 64;
-constexpr int32_t UNGUESSED_LOOKBACK = 64;   // chunks back k_round_pending looks for a diagonal
 constexpr int32_t LONG_GAP = 4096;   // literal gaps of the record text copied grid-wide
 constexpr int32_t CAND_CAP = 65536;  // early sweep: first-k-mer occurrences kept (more: full sweep later)
 // Frozen chains (k_chain_*): a committed frozen chunk's exit state is walked on over the rest of the
 // target by one wave that visits only "band hits" -- target positions whose k-mer occurs among the
 // reference k-mers within CH_BAND of the generation's P -- found by a grid scan.
-#ifndef SCCG_CH_BAND
-#define SCCG_CH_BAND 512
-#endif
-constexpr int CH_BAND = SCCG_CH_BAND;   // band half-width (reference positions around P)
+constexpr int CH_BAND = 512;           // band half-width (reference positions around P)
 constexpr int CH_TBITS = CH_BAND <= 2048 ? 13 : 14;   // band key table: 8192 / 16384 LDS slots (load <= 1/2)
-#ifndef SCCG_CH_GRID
-#define SCCG_CH_GRID 512
-#endif
-constexpr int CH_GRID = SCCG_CH_GRID;  // scan blocks (1024 threads, 16 positions each per step)
+constexpr int CH_GRID = 512;           // scan blocks (1024 threads, 16 positions each per step)
 constexpr int CH_HCAP = 4096;          // band hits kept per block and generation
 constexpr int32_t CHAIN_MCAP = 1 << 22;   // matches a chain may take
-#ifndef SCCG_CH_GENS_PER_SYNC
-#define SCCG_CH_GENS_PER_SYNC 4
-#endif
-constexpr int CH_GENS_PER_SYNC = SCCG_CH_GENS_PER_SYNC;    // generations queued per host check
-constexpr int ROUND_BATCH_DEFAULT = 1;   // rounds queued per host readback from ROUND_BATCH_FROM on (1: off; A/B pending)
-constexpr int ROUND_BATCH_FROM = 4;
+constexpr int CH_GENS_PER_SYNC = 4;    // generations queued per host check
 constexpr int FF_MIN_CHUNKS = 8;       // frozen-first start: chunk 0's walk stuck for at least this many chunks
-// SCCG_RECHUNK=1 (opt-in): a frozen-first (stuck, literal-heavy: T2T-like) target is walked again
-// in chunks of FF_CHUNK bases.  Its divergent stretches hold ~400 short matches per 16 Ki chunk,
-// each a latency-bound walk step, so the round's slowest chunks set the walk: the 100 Mb T2T-like
-// pair 10.4 -> 8.3 ms and 20 Mb pairs -20..-30 %.  But on the T2T-like whole genome (24 pairs at
-// UCSC lengths) the smaller chunks multiply the poorly-speculated ones that the rounds resolve one
-// by one: chr3 44 -> 231 ms (72 -> 323 rounds), chr6 33 -> 186 ms, genome 0.50 -> 0.86 s
-// (profiles/r03/rechunk_ab/) -- so the default keeps the size rule.
-constexpr int FF_CHUNK = 8192;
-#ifndef SCCG_CH_FF_SPAN
-#define SCCG_CH_FF_SPAN (32 * 1024)
-#endif
 // find-first generations scan at most CH_GRID * CH_FF_SPAN target positions (then the next one goes
 // on from there): a scan over the whole rest of the target kept every block before the hit busy
 // for its whole span (T2T-like 100 Mb pair: ~73 us per generation, 40 generations)
-constexpr int64_t CH_FF_SPAN = SCCG_CH_FF_SPAN;
+constexpr int64_t CH_FF_SPAN = 32 * 1024;
 constexpr int CH_MAX_GENS = 4096;      // generations per chain
 constexpr int MARCH_ROUNDS = 4;        // rounds settling <= 2 chunks each before a march chain
+constexpr int CHAIN_ROUND = 10;        // first round whose frozen chunks start a chain (see run_rounds)
 constexpr int64_t CH_DENSE_HITS = 32768;  // band hits of one generation that switch the chain to find-first generations
 constexpr int CH_DENSE_N = 32;         // hand back to the chunk rounds when CH_DENSE_N matches
 constexpr int32_t CH_DENSE_SPAN = 8192;   // fall within this many target bases (the walk is aligned again)
@@ -131,10 +100,7 @@ constexpr int32_t CH_DENSE_SPAN = 8192;   // fall within this many target bases 
 // finding matches is a trapped walk (chance hits in a low-complexity window nudging P every few kb,
 // e.g. the synthetic chr22 from 45.8 Mb): one wave then walks them serially (~4 us each), which the
 // rounds' trapped re-speculation resolves faster, so the chain hands back after this many matches.
-#ifndef SCCG_CH_HANDBACK
-#define SCCG_CH_HANDBACK 64
-#endif
-constexpr int CH_HANDBACK_N = SCCG_CH_HANDBACK;
+constexpr int CH_HANDBACK_N = 64;
 
 struct WalkPtrs {
     const uint8_t* R;
@@ -173,7 +139,6 @@ struct WalkPtrs {
     int32_t* lround;      // round for which the chunk was last put on the walk list
     int32_t* seedq;       // first match of the committed trajectory after its last re-seed
     int32_t* trapped;     // last fix-up walk (or frozen fill) of the chunk was trapped (TRAP_P)
-    int32_t stale_budget; // positions a stale-entry fix-up may walk without converging (0: no limit)
     int32_t* frozen;      // fix-up ended in a long literal run at the chunk end
     int32_t* flist;       // committed frozen chunks of the round
     int32_t* fy;          // per listed frozen chunk: first window hit after its exit (k_frozen_scan)
@@ -182,13 +147,11 @@ struct WalkPtrs {
                           // [12] trapped triggers of the round end, [13] frozen fills of the round end
     int32_t* trig;        // the round end's trapped triggers (RESPEC_MAX_TRIGGERS)
     int32_t* tflag;       // per chunk: round in which it was a trapped trigger (k_round_pending)
-    int32_t unguessed_spec;   // SCCG_UNGUESSED_SPEC: k_round_pending speculates chunks left without a trajectory
     int32_t* fa_j;        // the round end's frozen fills: chunks fa_j+1 .. fa_l literal with P fa_p (scal[13])
     int32_t* fa_l;
     int32_t* fa_p;
     int32_t* hintY;       // per chunk: a frozen scan's first window hit of P = hintP in this chunk (-1: none);
     int32_t* hintP;       // a walk at (x <= hintY, hintP) in the chunk may jump to hintY (all literal steps)
-    int32_t skip_hints;   // SCCG_SKIP_HINTS (default on)
     uint64_t* atab;
     uint32_t agen;            // anchor tag generation (one per call)
     int32_t adet;             // anchor slots written with atomicMax (SCCG_ANCHOR_DET, default off)
@@ -197,8 +160,7 @@ struct WalkPtrs {
     int32_t round;            // walk round of the launch (kernel argument copy)
     int32_t abits;
     const int64_t* dnR;       // early sweep: |R'| in device memory (nR is then only a bound)
-    int32_t astep;            // anchor sample stride
-    int32_t amulti;           // 1: second build pass marks repeated 32-mers
+    int32_t astep;            // ANCHOR_STEP (see anchor_samples)
     unsigned long long* fc;   // full-candidate scan scalars: [0] lmax [1] cnt [2] has0 [3] minkey [4] firsthit [5] firstexo
                               // [8..11] the same four for the batch's first position (k_presence + k_cand_reduce)
     unsigned long long* fcb;  // per presence block: 4 candidate statistics
@@ -248,10 +210,7 @@ __device__ __forceinline__ int32_t chunk_hi(const WalkPtrs& A, int32_t j) {
 // So most steps make no dependent HBM round trip at all; only an extension that runs past the copy
 // loads (and refreshes it).
 constexpr int WFBITS = 14;             // window pre-filter: 16384-bit Bloom filter, 3 hashes
-#ifndef WALK_LBV
-#define WALK_LBV 2048
-#endif
-constexpr int LBV = WALK_LBV;          // bytes of R' and of T' kept per wave (one HBM step loads them)
+constexpr int LBV = 2048;              // bytes of R' and of T' kept per wave (one HBM step loads them)
 constexpr int LBW = LBV / 256;         // dwords of each per lane and HBM step
 static_assert(LBW % 8 == 0, "whole 32-byte stretches per lane");
 constexpr int LEAD = 128;              // of which before the extension's start (the next window reaches back m)
@@ -259,8 +218,6 @@ static_assert(LEAD % (4 * LBW) == 0, "the lead is whole lanes' stretches");
 __device__ __forceinline__ uint32_t wf_h1(uint32_t key) { return slot_hash(key, WFBITS); }
 __device__ __forceinline__ uint32_t wf_h2(uint32_t key) { return (key * 0x85EBCA77u) >> (32 - WFBITS); }
 __device__ __forceinline__ uint32_t wf_h3(uint32_t key) { return (key * 0xC2B2AE3Du + 0x27D4EB2Fu) >> (32 - WFBITS); }
-typedef __attribute__((address_space(1))) void GVoid;
-typedef __attribute__((address_space(3))) void LVoid;
 struct WalkLds {
     uint32_t wbits[1 << (WFBITS - 5)];
     __attribute__((aligned(16))) uint8_t rbuf[LBV + 64];   // R'[rb0, rb0 + LBV)  (+ slack read by the unaligned word loads)
@@ -323,83 +280,6 @@ __device__ __forceinline__ int first_diff(const uint32_t (&r)[N], const uint32_t
 }
 __device__ __forceinline__ int first_diff32(const uint32_t (&r)[8], const uint32_t (&t)[8]) { return first_diff<8>(r, t); }
 
-// WALK_LCE_V (build option, A/B): 0 = lanes compare their own 32-byte stretches (the HBM step's
-// loads compared straight from registers); 1 = coalesced 16-byte lanes through the LDS copy (the
-// default since round 6: LDS bank-conflict cycles 65 -> 56 % of the LDS-active cycles, genome bench
-// 151.6-162.1 -> 166.4-172.8 Gbase/s interleaved on one box, gpurun_out/r06n, profiles/r06/).
-#ifndef WALK_LCE_V
-#define WALK_LCE_V 1
-#endif
-#if WALK_LCE_V == 0
-// longest common extension of R[a..] and T[b..], at most maxlen bytes (extend_alignment,
-// compression.cpp:27-34); whole wave.  First from the LDS copy when both starts lie in it (2 KiB
-// per pass); then from HBM, LBV bytes per round trip (lanes 0-3 load the LEAD bytes before the
-// stretch compared), every HBM step leaving its bytes in the copy.
-__device__ __forceinline__ int32_t wave_lce(const WalkPtrs& A, WalkLds& L, BufPos& B, int32_t a, int32_t b, int32_t maxlen) {
-    const int lane = lane_id();
-    if (maxlen <= 0) return 0;
-    int32_t off = 0;
-    if (a >= B.rb0 && b >= B.tb0 && a < B.rb0 + LBV && b < B.tb0 + LBV) {
-        int32_t avail = B.rb0 + LBV - a < B.tb0 + LBV - b ? B.rb0 + LBV - a : B.tb0 + LBV - b;
-        if (avail > maxlen) avail = maxlen;
-        for (int32_t base = 0; base < avail; base += 2048) {
-            const int32_t my = base + 32 * lane;
-            int32_t e = INT32_MAX;
-            if (my < avail) {
-                uint32_t r[8], t[8];
-                loadw_lds<8>(L.rbuf, a - B.rb0 + my, r);
-                loadw_lds<8>(L.tbuf, b - B.tb0 + my, t);
-                int pos = first_diff32(r, t);
-                if (avail - my < 32 && pos >= avail - my) pos = avail - my == maxlen - my ? avail - my : 32;
-                if (pos < 32) e = my + pos;
-            }
-            const unsigned long long sm = __ballot(e != INT32_MAX);
-            if (sm) {
-                const int32_t m = lane_val(e, first_lane(sm));
-                return m < maxlen ? m : maxlen;
-            }
-        }
-        if (avail >= maxlen) return maxlen;
-        off = avail;
-    }
-    while (off < maxlen) {
-        const int32_t lead = (a + off >= LEAD && b + off >= LEAD) ? LEAD : 0;
-        const int32_t sa = a + off - lead, sb = b + off - lead;
-        uint32_t r[LBW], t[LBW];
-        loadw<LBW>(A.R + sa + 4 * LBW * lane, r);
-        loadw<LBW>(A.T + sb + 4 * LBW * lane, t);
-        wave_sync();   // the copy's previous readers are done
-        {
-            uint4* dr = reinterpret_cast<uint4*>(L.rbuf) + (LBW / 4) * lane;
-            uint4* dt = reinterpret_cast<uint4*>(L.tbuf) + (LBW / 4) * lane;
-#pragma unroll
-            for (int i = 0; i < LBW / 4; i++) {
-                dr[i] = make_uint4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
-                dt[i] = make_uint4(t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
-            }
-        }
-        wave_sync();
-        B.rb0 = sa;
-        B.tb0 = sb;
-        const int32_t rel = 4 * LBW * lane - lead;   // this lane's bytes, from a + off
-        int32_t e = INT32_MAX;
-        if (rel >= 0 && rel < maxlen - off) {   // (LEAD is whole lanes' stretches: no lane straddles a + off)
-            int pos = first_diff<LBW>(r, t);
-            const int32_t lim = maxlen - off - rel;
-            if (lim < 4 * LBW && pos > lim) pos = lim;
-            if (pos < 4 * LBW) e = off + rel + pos;
-        }
-        const unsigned long long sm = __ballot(e != INT32_MAX);
-        if (sm) {
-            const int32_t m = lane_val(e, first_lane(sm));
-            return m < maxlen ? m : maxlen;
-        }
-        off += LBV - lead;
-    }
-    return maxlen;
-}
-
-#else
 // 16 bytes at byte offset off + 16 lane of an LDS byte array (off lane-uniform): three 8-byte reads
 // from the 8-byte aligned base below and one alignment for the whole wave (lane stride 16 bytes:
 // ds_read_b64 spreads a lane group over all 64 banks but for one pair -- a 32-byte lane stride,
@@ -445,7 +325,9 @@ __device__ __forceinline__ int32_t lds_first_diff(const uint8_t* rbuf, int32_t r
 // HBM, LBV bytes of each per round trip, loaded coalesced (16 bytes per lane and KiB, from 16-byte
 // aligned bases at most 15 bytes before the LEAD bytes kept ahead of the stretch) into the copy and
 // compared from there.  (Lanes loading their own 32-byte stretches took 18 dword loads per lane and
-// step, each touching 16 cache lines: with ~5 walk waves per SIMD the round trips queued to ~10 us.)
+// step, each touching 16 cache lines: with ~5 walk waves per SIMD the round trips queued to ~10 us.
+// Round 6, against lanes comparing those stretches straight from registers: LDS bank-conflict cycles
+// 65 -> 56 % of the LDS-active cycles, genome bench 151.6-162.1 -> 166.4-172.8 Gbase/s interleaved.)
 __device__ __forceinline__ int32_t wave_lce(const WalkPtrs& A, WalkLds& L, BufPos& B, int32_t a, int32_t b, int32_t maxlen) {
     const int lane = lane_id();
     if (maxlen <= 0) return 0;
@@ -484,7 +366,6 @@ __device__ __forceinline__ int32_t wave_lce(const WalkPtrs& A, WalkLds& L, BufPo
     return maxlen;
 }
 
-#endif   // WALK_LCE_V
 
 // the same from HBM only (no copy kept; 2 KiB per round trip)
 __device__ int32_t wave_lce_hbm(const uint8_t* __restrict__ R, int32_t a, const uint8_t* __restrict__ T, int32_t b,
@@ -614,9 +495,8 @@ __device__ void bloom_window(const RegWin& W, WalkLds& L) {
 // positions per wave step: 16 consecutive per lane, keys by shifting one packed code word; the
 // Bloom filter passes a superset, confirmed exactly against the register window in position order).
 constexpr int WIDE = 16;   // positions per lane per step (1024 per wave step)
-#ifndef WIDE_DEPTH
-#define WIDE_DEPTH 1       // steps whose words are in flight ahead of the one tested
-#endif
+constexpr int WIDE_DEPTH = 1;   // steps whose words are in flight ahead of the one tested (deeper
+                                // costs the walk registers it spills)
 // one step's 1024 positions from base: first hit (exact), or -1
 __device__ __forceinline__ int32_t wide_step(const WalkPtrs& A, const WalkLds& L, const RegWin& W, int32_t base, int32_t end,
                                              const uint32_t (&w)[8]) {
@@ -684,64 +564,6 @@ __device__ __forceinline__ int32_t wide_scan(const WalkPtrs& A, const WalkLds& L
     return end;
 }
 
-// Long literal scans (WIDE_RING): the words of the next 3 steps stream into LDS by LDS-DMA while a
-// step is tested -- a lone wave scanning a stuck stretch otherwise waits a whole HBM round trip
-// per 1024 positions (the register prefetch is one step deep: deeper costs the walk registers it
-// spills).  The four 1040-byte ring slots reuse the wave's R'/T' copy (invalidated: after a long
-// literal stretch it holds nothing the next step needs).  A slot is read with an inline-asm
-// ds_read after a counted vmcnt wait (a plain LDS read behind LDS-DMA gets a vmcnt(0) from the
-// compiler, which would drain the prefetch every step).  Every exit drains the DMA first.
-#ifndef WIDE_RING
-#define WIDE_RING 0
-#endif
-constexpr int RING_SLOT = 1040;          // 1024 positions + the k - 1 <= 15 bytes after them (16)
-constexpr int32_t RING_MIN = 8192;       // scans at least this long take the ring
-__device__ __forceinline__ uint8_t* ring_slot(WalkLds& L, int i) {
-    return ((i & 2) ? L.tbuf : L.rbuf) + (i & 1) * RING_SLOT;
-}
-__device__ __forceinline__ void ring_issue(const WalkPtrs& A, WalkLds& L, int i, int32_t base) {
-    const int lane = lane_id();
-    uint8_t* slot = ring_slot(L, i);
-    __builtin_amdgcn_global_load_lds((GVoid*)(A.T + base + 16 * lane), (LVoid*)slot, 16, 0, 0);
-    if (lane == 0) __builtin_amdgcn_global_load_lds((GVoid*)(A.T + base + 1024), (LVoid*)(slot + 1024), 16, 0, 0);
-}
-// wait until at most 2 * ahead LDS-DMA instructions are outstanding (each step issues two)
-__device__ __forceinline__ void ring_wait(int ahead) {
-    if (ahead >= 3) __builtin_amdgcn_s_waitcnt(0x0F76);
-    else if (ahead == 2) __builtin_amdgcn_s_waitcnt(0x0F74);
-    else if (ahead == 1) __builtin_amdgcn_s_waitcnt(0x0F72);
-    else __builtin_amdgcn_s_waitcnt(0x0F70);
-}
-__device__ __forceinline__ void ring_read(WalkLds& L, int i, uint32_t (&w)[8]) {
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    const uint32_t addr = (uint32_t)(size_t)(ring_slot(L, i) + 16 * lane_id());
-    v4u a, b;
-    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=v"(a), "=v"(b) : "v"(addr) : "memory");
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-__device__ int32_t wide_scan_ring(const WalkPtrs& A, WalkLds& L, BufPos& B, const RegWin& W, int32_t x, int32_t end) {
-    B.rb0 = NO_BUF;   // the copy's space becomes the ring
-    B.tb0 = NO_BUF;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (this wave's earlier LDS accesses are done)
-    wave_sync();
-    const int32_t nsteps = (end - x + 1023) >> 10;
-    for (int d = 0; d < 3 && d < nsteps; d++) ring_issue(A, L, d, x + 1024 * d);
-    int32_t res = end;
-    for (int32_t st = 0; st < nsteps; st++) {
-        if (st + 3 < nsteps) ring_issue(A, L, (st + 3) & 3, x + 1024 * (st + 3));
-        const int32_t left = nsteps - 1 - st;
-        ring_wait(left < 3 ? left : 3);
-        uint32_t w[8];
-        ring_read(L, st & 3, w);
-        const int32_t y = wide_step(A, L, W, x + 1024 * st, end, w);
-        if (y >= 0) { res = y; break; }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // no DMA may land in the copy's space later
-    wave_sync();
-    return res;
-}
-
 // ---------------------------------------------------------------------------------------------
 // the chunk walk (one wave per chunk)
 // ---------------------------------------------------------------------------------------------
@@ -763,9 +585,7 @@ __device__ __forceinline__ KArgPtr kargs() {
 #define KC (kargs())
 
 constexpr int DBG_SLOTS = 16;   // ticks, matches, batches, wides, windows, cands, ext bases, t_win, t_find, t_cand, t_tail
-#ifndef WALK_WAVES_PER_EU
-#define WALK_WAVES_PER_EU 5
-#endif
+constexpr int WALK_WAVES_PER_EU = 5;
 // nlist_dev (optional): the list length from device memory (a round queued before the host knows it)
 // CARRY: the carry launch of a round (list = KC->clist): each listed chunk is walked from its
 // predecessor's staged exit and committed here, and the walk carries on while the rule allows.
@@ -873,16 +693,12 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
     // a frozen scan found the first window hit of this P in the chunk: the steps before it are
     // literal (the scan covered every position from the frozen chunk's exit on), so the walk
     // starts there -- the trajectory and exit are those of the walk from x
-    if (!CARRY && kind == KIND_FIX && A.skip_hints) {
+    if (!CARRY && kind == KIND_FIX) {
         const int32_t hy = uni(KC->hintY[j]);
         if (hy > x && hy < scan_end && uni(KC->hintP[j]) == P) x = hy;
     }
-    // stale entry (predecessor re-walked in this round): converge within the budget or give up
-    const bool stale = !CARRY && A.stale_budget > 0 && kind == KIND_FIX && j > 0 && KC->lround[j - 1] == A.round;
-    int32_t budget_end = stale && x + A.stale_budget < scan_end ? x + A.stale_budget : scan_end;
     int32_t old_seedq = cb >= 0 ? uni(KC->seedq[j]) : 0;
     int32_t seed_x = x, seedq = 0;
-    bool truncated = false;
     // the previous trajectory (fix-ups), 64 entries at a time in registers: lane i holds entry cq0 + i
     int32_t cq0 = -1, ctv = INT32_MAX, cpv = 0, clv = 0;
     auto load_prev = [&](int32_t from) {
@@ -907,7 +723,6 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
     // only iterates in the carry instantiation, so the main walk's registers stay as they were.)
     for (;;) {
     while (x < scan_end) {
-        if (x >= budget_end) { truncated = true; break; }
         if (DBG) tick(9);
         // the probe: keys of the 64 target positions from x (from the LDS copy when it holds them)
         const int32_t y_l = x + lane;
@@ -936,7 +751,7 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
         if (hl < 0) {
             x = (x + 64 < scan_end) ? x + 64 : scan_end;
             if (x < scan_end) {
-                int32_t wend = budget_end;
+                int32_t wend = scan_end;
                 if (first_spec) {   // re-seed a stuck first guess (see RESEED_GAP)
                     if (x - (lme > seed_x ? lme : seed_x) >= RESEED_GAP) {
                         seed_x = x;
@@ -954,8 +769,7 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
                 if (bloomP != P) { bloom_window(W, L); bloomP = P; }
                 if (DBG) tick(10);
                 const int32_t x0 = x;
-                if (WIDE_RING && wend - x >= RING_MIN) x = wide_scan_ring(A, L, B, W, x, wend);
-                else x = wide_scan(A, L, W, x, wend);   // exact: x is a hit (or wend)
+                x = wide_scan(A, L, W, x, wend);   // exact: x is a hit (or wend)
                 if (DBG) { dbg_c[2]++; dbg_c[12] += x - x0; tick(11); }
             }
             continue;
@@ -1059,14 +873,6 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
             d[14] = (uint64_t)A.round;
             d[15] = dbg_t0;   // start (wall clock), for the launch's start spread
         }
-        if (lane == 0 && truncated) {   // nothing to commit; the chunk stays pending
-            KC->conv[j] = 0;
-            KC->changed[j] = 0;
-            KC->walked[j] = A.round;
-            KC->frozen[j] = 0;
-            KC->status[j] = ST_TRUNC;
-            return;
-        }
         if (lane == 0) {
             KC->cnt[ob][j] = n;
             if (cb < 0) {   // speculative: the trajectory is the chunk's first, take it as is
@@ -1083,7 +889,6 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
             }
             KC->status[j] = converged ? ST_CONV : ST_DONE;
         }
-        if (truncated) return;
         // carry on only from a fix-up whose commit is certain (k_commit takes it: its predecessor is
         // not listed, and -- by the rule below -- not carried into either), and not where the
         // frozen scan (frozen end) or the trapped re-speculation (k_round_respec) resolves faster
@@ -1124,7 +929,6 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
     lo_j = chunk_lo(A, j);
     hi_j = chunk_hi(A, j);
     scan_end = hi_j < lastk + 1 ? hi_j : lastk + 1;
-    budget_end = scan_end;
     cb = uni(KC->cur[j]);
     ob = 1 - cb;
     cc = uni(KC->cnt[cb][j]);
@@ -1170,7 +974,7 @@ __global__ void k_commit(WalkPtrs A, const int32_t* __restrict__ list, int32_t n
     if (blockIdx.x == 0 && threadIdx.x == 0) A.scal[11] = 0;   // the round's carry list was consumed
     for (int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x); i < nlist; i += (int32_t)(gridDim.x * blockDim.x)) {
         const int32_t j = list[i];
-        if (A.kind[j] == KIND_SPEC || A.status[j] == ST_ESC || A.status[j] == ST_TRUNC) continue;
+        if (A.kind[j] == KIND_SPEC || A.status[j] == ST_ESC) continue;
         const int32_t round = A.round;
         const bool pred_changed = j > 0 && A.walked[j - 1] == round && A.changed[j - 1];
         if (!(A.conv[j] || !pred_changed)) continue;
@@ -1433,31 +1237,8 @@ __global__ __launch_bounds__(256) void k_round_pending(WalkPtrs A) {
     const bool pend = ex != INVALID && !(ex == ux && ep == up);
     if (!pend) {
         if (lr == next) A.lround[j] = A.round;   // listed by an earlier batch of this round
-        // A chunk without a trajectory after its first speculation (no anchor vote anywhere in it:
-        // a tandem array, whose 32-mers all repeat, or an escalated speculation) waits until its
-        // predecessor settles, and a run of them is then resolved one chunk after another.
-        // Speculate it instead from the diagonal of the nearest earlier chunk that has an exit
-        // (<= UNGUESSED_LOOKBACK back): inside an array the walk keeps to one diagonal, and the
-        // window (+-m) around the guess snaps onto it at the first match.  (Exactness is the
-        // loop's: speculation only decides what the next rounds re-walk.)  Opt-in
-        // (SCCG_UNGUESSED_SPEC=1): on the T2T-like genome a wrong-diagonal speculation feeds the
-        // next fix-up a garbage entry whose frozen scan runs to the target's end (chr2 68 ms ->
-        // 0.7 s), and the synthetic tandem-array walk (walk_micro.py dense) kept its 55 rounds --
-        // its chunks do get votes, onto the wrong copies of the 171-bp unit.
-        if (A.unguessed_spec && j > 0 && ux != NEVER && A.exitX[j] == INVALID) {
-            int32_t r = -1;
-            for (int32_t q = j - 1; q >= 0 && q >= j - UNGUESSED_LOOKBACK; q--)
-                if (A.exitX[q] != INVALID) { r = q; break; }
-            if (r >= 0) {
-                const int64_t d = (int64_t)A.exitP[r] - A.exitX[r] + 1;
-                int64_t gp = (int64_t)chunk_lo(A, j) - 1 + d;
-                gp = gp < 0 ? 0 : (gp > A.nR - 1 ? A.nR - 1 : gp);
-                A.kind[j] = KIND_SPEC;
-                A.guess[j] = (int32_t)gp;
-                A.lround[j] = next;
-                A.plist[atomicAdd(&A.scal[0], 1)] = j;
-            }
-        }
+        // (a chunk without a trajectory after its first speculation -- no anchor vote anywhere in
+        // it -- waits until its predecessor settles)
         return;
     }
     A.snapX[j] = ex;
@@ -1988,21 +1769,27 @@ __device__ __forceinline__ void anchor_put(const WalkPtrs& A, uint64_t key, uint
     else A.atab[key >> (64 - A.abits)] = anchor_slot(A, key, pos);   // (SCCG_ANCHOR_DET=0: last writer wins)
 }
 
-// pass 1 (mark = false): store every sample; pass 2 (mark = true): flag repeated 32-mers
-template <bool MARK>
-__global__ void k_anchor_build(WalkPtrs A) {
-    const int64_t ns = A.nR >= ANCHOR_K ? ((int64_t)A.nR - ANCHOR_K) / A.astep + 1 : 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t p = (int32_t)(i * A.astep);
-        uint64_t code;
-        if (!code32<true>(A.R + p, code)) continue;
-        const uint64_t key = mix64(code);
-        if (!MARK) {
-            anchor_put(A, key, (uint32_t)p);
-        } else {   // (MULTI is the largest position: the mark is an atomicMax too)
-            const uint64_t v = A.atab[key >> (64 - A.abits)];
-            if ((v >> 32) == (anchor_slot(A, key, 0) >> 32) && (uint32_t)v != (uint32_t)p) anchor_put(A, key, A_MULTI);
+// The samples of a first-step sweep's 64-position stretch from p0, out of its packed words: the
+// 2-bit codes (cw) and non-ACGT flags (dw), 4 bases per word; acc: some word of the stretch is
+// flagged.  nR: |R'|.  (A.astep is ANCHOR_STEP, 64: one sample, at p0.  It stays a kernel argument:
+// with the constant folded in, k_key0<true> took 104 VGPRs for 82 and lost a wave per SIMD.)
+__device__ __forceinline__ void anchor_samples(const WalkPtrs& A, int64_t nR, int64_t p0, const uint32_t (&cw)[20],
+                                               const uint32_t (&dw)[20], uint32_t acc) {
+    const int nh = A.astep == 32 ? 2 : 1;   // (samples at p0 and p0 + 32, or p0 only)
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const int64_t p = p0 + 32 * h;
+        if (h >= nh || p + ANCHOR_K > nR) break;
+        uint64_t code = 0;
+        uint32_t bad = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            code |= (uint64_t)cw[8 * h + i] << (8 * i);
+            bad |= dw[8 * h + i];
         }
+        if (acc && bad) continue;
+        const uint64_t key = mix64(code);
+        anchor_put(A, key, (uint32_t)p);
     }
 }
 
@@ -2157,7 +1944,8 @@ __global__ void k_fullc(WalkPtrs A, int32_t y, int32_t P, int pass) {
 constexpr int PB = 1024;
 constexpr int PBBITS = 11;
 constexpr int PRESENCE_GRID = 1024;   // blocks of a presence sweep (each first builds the batch's LDS tables)
-constexpr int KEY0_GRID_MAX = 16384;  // blocks of the first-step sweep (no LDS tables: as many as pay)
+constexpr unsigned KEY0_GRID = 1024;  // blocks of the first-step sweep
+constexpr int KEY0_GRID_MAX = 16384;  // (fcb holds statistics for this many: the workspace layout's bound)
 constexpr int PFBITS = 17;   // presence pre-filter: 2^17-bit LDS bitmap of the batch's keys
 
 // candidate statistics of one target position (compression.cpp:114-130 over ALL candidates):
@@ -2250,7 +2038,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_presence(WalkPtrs A, int32_t x0,
 // The usual first step: does the target's first k-mer (x0) occur in R' at all, and the candidate
 // statistics if so.  One key, no tables: a plain compare per reference position, so this sweep
 // runs at streaming speed; k_presence (the general batch search) runs only when it finds nothing.
-// ANCH: the same pass also stores the anchor samples (every 32nd or 64th position, astep 32 / 64)
+// ANCH: the same pass also stores the anchor samples (every ANCHOR_STEP-th position)
 // -- their 2-bit codes are the words the sweep already packed, so the anchor index costs no extra
 // read of R'.
 template <bool ANCH>
@@ -2268,23 +2056,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_key0(WalkPtrs A, int32_t x0) {
                           best = cb_merge(best, CandBest{l, 1u, c == 0 ? 1u : 0u, c ? pick_key((int32_t)c, -1) : ~0ull});
                       },
                       [&](int64_t p0, const uint32_t (&cw)[20], const uint32_t (&dw)[20], uint32_t acc) {
-                          if (!ANCH) return;
-                          const int nh = A.astep == 32 ? 2 : 1;   // (samples at p0 and p0 + 32, or p0 only)
-#pragma unroll
-                          for (int h = 0; h < 2; h++) {
-                              const int64_t p = p0 + 32 * h;
-                              if (h >= nh || p + ANCHOR_K > A.nR) break;
-                              uint64_t code = 0;
-                              uint32_t bad = 0;
-#pragma unroll
-                              for (int i = 0; i < 8; i++) {
-                                  code |= (uint64_t)cw[8 * h + i] << (8 * i);
-                                  bad |= dw[8 * h + i];
-                              }
-                              if (acc && bad) continue;
-                              const uint64_t key = mix64(code);
-                              anchor_put(A, key, (uint32_t)p);
-                          }
+                          if (ANCH) anchor_samples(A, A.nR, p0, cw, dw, acc);
                       });
     }
     best = cb_wave(best);
@@ -2352,7 +2124,6 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_first_kmer(const uint8_t* __rest
     if (threadIdx.x == 0) *reinterpret_cast<int32_t*>(kb + KB_COUNT) = found < k ? (int32_t)found : k;
 }
 
-template <bool ANCH>
 __global__ __launch_bounds__(SCCG_BLOCK) void k_sweep_early(WalkPtrs A) {
     const int k = A.k, kp = A.kp;
     const int64_t nR = A.dnR ? *A.dnR : A.nR;   // |R'| (A.nR only bounds it)
@@ -2366,23 +2137,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_sweep_early(WalkPtrs A) {
                       if (i < (unsigned long long)CAND_CAP) A.cand[i] = (int32_t)c;
                   },
                   [&](int64_t p0, const uint32_t (&cw)[20], const uint32_t (&dw)[20], uint32_t acc) {
-                      if (!ANCH) return;
-                      const int nh = A.astep == 32 ? 2 : 1;   // (samples at p0 and p0 + 32, or p0 only)
-#pragma unroll
-                      for (int h = 0; h < 2; h++) {
-                          const int64_t p = p0 + 32 * h;
-                          if (h >= nh || p + ANCHOR_K > nR) break;
-                          uint64_t code = 0;
-                          uint32_t bad = 0;
-#pragma unroll
-                          for (int i = 0; i < 8; i++) {
-                              code |= (uint64_t)cw[8 * h + i] << (8 * i);
-                              bad |= dw[8 * h + i];
-                          }
-                          if (acc && bad) continue;
-                          const uint64_t key = mix64(code);
-                          anchor_put(A, key, (uint32_t)p);
-                      }
+                      anchor_samples(A, nR, p0, cw, dw, acc);
                   });
 }
 
@@ -2774,15 +2529,31 @@ int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
 }
-int anchor_step() {
-    static const int v = [] { const int x = env_int("SCCG_ANCHOR_STEP", ANCHOR_STEP_DEFAULT); return x >= 8 && x <= 1024 ? x : ANCHOR_STEP_DEFAULT; }();
-    return v;
+// the diagnostics variables, read once per process (none of them changes what the walk computes)
+struct WalkEnv {
+    bool debug;         // SCCG_DEBUG: phase clocks, the instrumented k_walk<true, *>, per-round dumps
+    bool phases;        // SCCG_DEBUG_PHASES: also per-phase clocks inside the walk step
+    int debug_round;    // SCCG_DEBUG_ROUND: keep the per-chunk counters of that round only (-1: the last)
+    int debug_rounds;   // SCCG_DEBUG_ROUNDS: rounds whose chunk states are dumped (default 3)
+    bool all_rounds;    // SCCG_DEBUG_ALLROUNDS: the cost profile for every round, not rounds 1 and 2
+    int debug_chunk;    // SCCG_DEBUG_CHUNK: one chunk's trajectory buffers per round (-1: none)
+    int round_log;      // SCCG_ROUND_LOG: 1 a status line per round, 2 with a digest of the chunk states
+};
+const WalkEnv& walk_env() {
+    static const WalkEnv e = [] {
+        const char* rl = getenv("SCCG_ROUND_LOG");
+        return WalkEnv{getenv("SCCG_DEBUG") != nullptr,       getenv("SCCG_DEBUG_PHASES") != nullptr,
+                       env_int("SCCG_DEBUG_ROUND", -1),       env_int("SCCG_DEBUG_ROUNDS", 3),
+                       getenv("SCCG_DEBUG_ALLROUNDS") != nullptr, env_int("SCCG_DEBUG_CHUNK", -1),
+                       rl ? (rl[0] == '2' ? 2 : 1) : 0};
+    }();
+    return e;
 }
+
 int anchor_bits(int64_t nR) {
-    static const int load = [] { const int x = env_int("SCCG_ANCHOR_LOAD", ANCHOR_LOAD_DEFAULT); return x >= 1 && x <= 16 ? x : ANCHOR_LOAD_DEFAULT; }();
-    // SCCG_ANCHOR_SHIFT (tuning runs): the table's size in powers of two away from `load` slots per sample
+    // SCCG_ANCHOR_SHIFT (tests): the table's size in powers of two away from ANCHOR_LOAD slots per sample
     static const int shift = [] { const int x = env_int("SCCG_ANCHOR_SHIFT", 0); return x >= -4 && x <= 4 ? x : 0; }();
-    int64_t want = load * (nR / anchor_step() + 1);
+    int64_t want = ANCHOR_LOAD * (nR / ANCHOR_STEP + 1);
     int b = 10;
     while ((1ll << b) < want && b < 34) b++;
     b += shift;
@@ -2804,11 +2575,7 @@ WalkPtrs carve(void* ws, size_t ws_bytes, const uint8_t* R, int64_t nR, const ui
     const size_t C = (size_t)A.C, cap = (size_t)A.cap;
     // front: what depends on R' alone (the early sweep fills it before |T'| is known)
     A.abits = abits ? abits : anchor_bits(nR);   // (an early sweep sized it from a bound of |R'|)
-    A.astep = anchor_step();
-    {
-        static const int multi = env_int("SCCG_ANCHOR_MULTI", 0);
-        A.amulti = multi;
-    }
+    A.astep = ANCHOR_STEP;
     A.atab = c.take<uint64_t>((size_t)1 << A.abits);
     A.fc = c.take<unsigned long long>(16);
     A.fcb = c.take<unsigned long long>(4 * KEY0_GRID_MAX);
@@ -2843,7 +2610,6 @@ WalkPtrs carve(void* ws, size_t ws_bytes, const uint8_t* R, int64_t nR, const ui
     A.tflag = c.take<int32_t>(C);
     A.fa_j = c.take<int32_t>(FROZEN_MAX); A.fa_l = c.take<int32_t>(FROZEN_MAX); A.fa_p = c.take<int32_t>(FROZEN_MAX);
     A.hintY = c.take<int32_t>(C); A.hintP = c.take<int32_t>(C);
-    A.skip_hints = env_int("SCCG_SKIP_HINTS", 1);
     A.flat_off = c.take<int64_t>(C + 1);
     const size_t maxm = (size_t)(nT / k + 2);
     A.ft = c.take<int32_t>(maxm); A.fp = c.take<int32_t>(maxm); A.fl = c.take<int32_t>(maxm);
@@ -2969,7 +2735,7 @@ int run_chain(WalkPtrs& A, hipStream_t s, int* gens, bool* trapped, bool* starte
     }
     *gens = cs[8];
     *trapped = cs[5] == 2 && cs[3] >= CH_HANDBACK_N;
-    if (getenv("SCCG_DEBUG"))
+    if (walk_env().debug)
         fprintf(stderr, "[chain] from chunk %d (x %d, P %d): %d generations, %d matches, end x %d P %d, reason %d\n", cs[4], cs[9],
                 cs[10], cs[8], cs[3], cs[1], cs[2], cs[5]);
     return 0;
@@ -3025,11 +2791,6 @@ int resolve_escalations(WalkPtrs& A, hipStream_t s, std::vector<int32_t>* resume
 size_t walk_workspace_bytes(int64_t nR, int64_t nT, int k, int chunk) {
     size_t used = 0;
     carve(nullptr, 0, nullptr, nR, nullptr, nT, k, 100, chunk, &used);
-    if (chunk > FF_CHUNK) {   // room for a frozen-first walk re-chunked to FF_CHUNK
-        size_t used2 = 0;
-        carve(nullptr, 0, nullptr, nR, nullptr, nT, k, 100, FF_CHUNK, &used2);
-        if (used2 > used) used = used2;
-    }
     return used + 4096;
 }
 
@@ -3075,12 +2836,8 @@ struct Early {   // an early sweep queued by global_sweep_early
 thread_local Early g_early;
 
 unsigned first_sweep_grid(const WalkPtrs& A) {
-    static const unsigned key0_grid = [] {
-        const char* e = getenv("SCCG_KEY0_GRID");
-        const int v = e ? atoi(e) : 1024;
-        return (unsigned)(v >= 64 && v <= KEY0_GRID_MAX ? v : 1024);
-    }();
-    return grid_for(A.nR - A.k + 1, 256 * FC_PER_T) > key0_grid ? key0_grid : grid_for(A.nR - A.k + 1, 256 * FC_PER_T);
+    const unsigned g = grid_for(A.nR - A.k + 1, 256 * FC_PER_T);
+    return g > KEY0_GRID ? KEY0_GRID : g;
 }
 
 // the anchor table's generation for this call (a fresh workspace is cleared once; afterwards every
@@ -3121,17 +2878,10 @@ int queue_prepare(WalkPtrs& A, const void* ws, hipStream_t s) {
     if (!walkable) return 0;
     const unsigned gsweep = first_sweep_grid(A);
     RC(anchor_generation(A, ws, s));
-    // the usual first step: x0 = 0's own k-mer (statistics land in fc[4..11]); with the default
-    // sample stride the same sweep stores the anchor samples
-    const bool fused = A.astep == 32 || A.astep == 64;
-    if (fused) PROF_LAUNCH(PROF_ANCHOR, s, k_key0<true>, dim3(gsweep), dim3(SCCG_BLOCK), 0, s, A, 0);
-    else hipLaunchKernelGGL(k_key0<false>, dim3(gsweep), dim3(SCCG_BLOCK), 0, s, A, 0);
+    // the usual first step: x0 = 0's own k-mer (statistics land in fc[4..11]); the same sweep stores
+    // the anchor samples
+    PROF_LAUNCH(PROF_ANCHOR, s, k_key0<true>, dim3(gsweep), dim3(SCCG_BLOCK), 0, s, A, 0);
     hipLaunchKernelGGL(k_cand_reduce, dim3(1), dim3(1024), 0, s, A, (int)gsweep, 0);
-    SCCG_HIP(hipGetLastError());
-    const int64_t ns = (int64_t)A.nR / A.astep + 1;
-    const unsigned ga = grid_for(ns, 256) > 8192 ? 8192 : grid_for(ns, 256);
-    if (!fused) PROF_LAUNCH(PROF_ANCHOR, s, k_anchor_build<false>, dim3(ga), dim3(256), 0, s, A);
-    if (A.amulti) hipLaunchKernelGGL(k_anchor_build<true>, dim3(ga), dim3(256), 0, s, A);
     // (the chunks' first guesses are voted by the round-1 walk itself: anchor_diag at each chunk start)
     SCCG_HIP(hipGetLastError());
     return 0;
@@ -3140,20 +2890,13 @@ int queue_prepare(WalkPtrs& A, const void* ws, hipStream_t s) {
 WalkPtrs make_ptrs(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nTp, int k, int m, int chunk, void* ws,
                    size_t ws_bytes, size_t* used, int abits = 0) {
     WalkPtrs A = carve(ws, ws_bytes, Rp, nRp, Tp, nTp, k, m, chunk, used, abits);
-    if (!getenv("SCCG_DEBUG")) A.dbg = nullptr;   // per-chunk counters only in diagnostic runs
-    A.dbg_phases = getenv("SCCG_DEBUG_PHASES") != nullptr;
-    A.dbg_round = getenv("SCCG_DEBUG_ROUND") ? atoi(getenv("SCCG_DEBUG_ROUND")) : -1;
-    static const int32_t sb = [] {
-        const char* e = getenv("SCCG_STALE_BUDGET");
-        return e ? atoi(e) : STALE_BUDGET_DEFAULT;
-    }();
-    A.stale_budget = sb;
+    if (!walk_env().debug) A.dbg = nullptr;   // per-chunk counters only in diagnostic runs
+    A.dbg_phases = walk_env().phases;
+    A.dbg_round = walk_env().debug_round;
     // (SCCG_ANCHOR_DET=1: atomicMax slots -- the same votes on every run, but the genome bench's
     // sweep took +1.2 ms per step for the read-modify-writes, and the rounds still vary with the
     // chains' timing-dependent generations; off by default)
     A.adet = env_int("SCCG_ANCHOR_DET", 0);
-    static const int32_t ug = getenv("SCCG_UNGUESSED_SPEC") != nullptr;
-    A.unguessed_spec = ug;
     return A;
 }
 
@@ -3175,15 +2918,7 @@ int global_sweep_early(const uint8_t* Rp, int64_t nRp, const int64_t* d_nRp, con
     RC(anchor_generation(A, ws, s));
     RC(set_u64(A.fc + 12, {0, 0}, s));
     hipLaunchKernelGGL(k_first_kmer, dim3(1), dim3(SCCG_BLOCK), 0, s, tgt_fa, tn, d_hdr, k, (int64_t)1 << 20, A.kb);
-    const unsigned g = first_sweep_grid(A);
-    if (A.astep == 32 || A.astep == 64) {
-        PROF_LAUNCH(PROF_ANCHOR, s, k_sweep_early<true>, dim3(g), dim3(SCCG_BLOCK), 0, s, A);
-    } else {
-        hipLaunchKernelGGL(k_sweep_early<false>, dim3(g), dim3(SCCG_BLOCK), 0, s, A);
-        const int64_t ns = (int64_t)A.nR / A.astep + 1;
-        const unsigned ga = grid_for(ns, 256) > 8192 ? 8192 : grid_for(ns, 256);
-        PROF_LAUNCH(PROF_ANCHOR, s, k_anchor_build<false>, dim3(ga), dim3(256), 0, s, A);
-    }
+    PROF_LAUNCH(PROF_ANCHOR, s, k_sweep_early, dim3(first_sweep_grid(A)), dim3(SCCG_BLOCK), 0, s, A);
     SCCG_HIP(hipGetLastError());
     g_early = Early{ws, Rp, nRp, k, A.agen, A.abits};
     return 0;
@@ -3205,11 +2940,6 @@ int global_prepare(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nT
         if (A.nR >= A.k && A.nT >= A.k) {
             hipLaunchKernelGGL(k_cand_stats, dim3(CAND_STATS_GRID), dim3(SCCG_BLOCK), 0, s, A);
             hipLaunchKernelGGL(k_cand_stats_fin, dim3(1), dim3(1024), 0, s, A, CAND_STATS_GRID);
-            if (A.amulti) {
-                const int64_t ns = (int64_t)A.nR / A.astep + 1;
-                const unsigned ga = grid_for(ns, 256) > 8192 ? 8192 : grid_for(ns, 256);
-                hipLaunchKernelGGL(k_anchor_build<true>, dim3(ga), dim3(256), 0, s, A);
-            }
             SCCG_HIP(hipGetLastError());
         }
     } else {
@@ -3220,11 +2950,6 @@ int global_prepare(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nT
 }
 
 namespace {
-// A frozen-first walk found at a chunk size above FF_CHUNK is restarted at FF_CHUNK (a fresh call on
-// the same workspace: the carve, the preparation and every chunk's state are laid out again).  The
-// restart keeps what the first attempt learned or handed out: the exact first step, the caller's
-// resolved text position (EmitTarget::resolve is called once per compress) and round1_queued.
-constexpr int WALK_RECHUNK = -2;
 // A range walk (sccg_walk_range): the global walk from state (x0, P0) until the first index >= x_end
 // (orc_walk_range's contract, compression.cpp:64-161 entered mid-way), on chunks covering
 // [x0, min(x_end, |T'|)).  P0 == -1 (ungated) only at x0 == 0: the usual exact first step.  Chains,
@@ -3234,619 +2959,368 @@ struct RangeWalk {
     int64_t x0 = 0, P0 = -1, x_end = 0;
     int64_t exit_x = 0, exit_P = -1;        // out
 };
-struct Rechunk {
-    bool on = false;                        // this is the restart
-    bool resolved = false;                  // late_out->resolve was called: its output pointer
-    uint8_t* out = nullptr;
-    bool r1 = false;                        // late_out->round1_queued was called
-    int32_t first_y = 0, first_p = 0, first_l = 0;
-};
 
-int match_and_emit_impl(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nTp, int k, int m, int chunk,
-                        void* ws, size_t ws_bytes, uint8_t* out, int64_t* out_len, WalkResult* res, hipStream_t s,
-                        bool abs_p, const EmitTarget* late_out, bool keep_flat, Rechunk* rt, RangeWalk* rw = nullptr) {
-    if (m < 0 || 2 * m + 1 > WCAP || k > KMAX || k < 1) return SCCG_E_UNSUPPORTED;
-    const bool range = rw != nullptr;
-    if (range && (rw->x0 < 0 || rw->P0 < -1 || (rw->P0 == -1 && rw->x0 != 0) || rw->x0 > nTp || rw->P0 >= nRp))
-        return SCCG_E_UNSUPPORTED;
-    const Prepared g = g_prep;   // queued by global_prepare (the caller ordered s after it)
-    g_prep = Prepared{};
-    const bool prepared = g.ws == ws && g.R == Rp && g.T == Tp && g.nR == nRp && g.nT == nTp && g.k == k && g.m == m &&
-                          g.chunk == chunk;
-    size_t used = 0;
-    WalkPtrs A = make_ptrs(Rp, nRp, Tp, nTp, k, m, chunk, ws, ws_bytes, &used, prepared ? g.abits : 0);
-    if (used > ws_bytes) return SCCG_E_INTERNAL;
-    res->rounds = 0;
-    res->chains = 0;
-    res->n_matches = 0;
-    const int32_t lastk = (int32_t)nTp - k;
-    // a range walk's exit when it takes no match: literal steps up to min(x_end, |T'| - k + 1)
-    auto literal_exit = [&](int64_t from) -> int64_t {
-        const int64_t lim = rw->x_end < (int64_t)lastk + 1 ? rw->x_end : (int64_t)lastk + 1;
-        return from < lim ? lim : from;
-    };
-    if (range) {
-        const int64_t xe = rw->x_end < nTp ? rw->x_end : nTp;
-        A.xlo = (int32_t)rw->x0;
-        A.xhi = (int32_t)(xe > rw->x0 ? xe : rw->x0);
-        A.C = (int32_t)(((int64_t)A.xhi - A.xlo + chunk - 1) / chunk);
-        if (A.C < 1) A.C = 1;
-        g_last_n = 0;
-        if (nRp < k || lastk < 0) {   // no k-mer to probe: every step is a literal
-            rw->exit_x = literal_exit(rw->x0);
-            rw->exit_P = rw->P0;
-            return 0;
-        }
-    }
-    res->chunks = A.C;
+// One call of the walk driver (match_and_emit_impl): what its phases share.
+struct WalkRun {
+    WalkPtrs A;
+    hipStream_t s;
+    WalkResult* res;
+    const EmitTarget* late_out;
+    RangeWalk* rw;       // null: the whole target
+    uint8_t* out;        // the record text's place (with late_out: known once resolve_out ran)
+    bool abs_p, keep_flat;
+    const uint8_t* Tp;
+    int64_t nTp;
+    int32_t lastk;       // last target position with a k-mer
+    int32_t first_y = INVALID, first_p = 0, first_l = 0;   // the exact first (ungated) match
+    int32_t startX = 0, startP = INVALID;                  // the walk's state behind it
+    bool pre_round = false;     // rounds 1 and 2 went out before the first readback
+    bool spec_queued = false;   // ... with round 2's record text behind them
+    bool spec_text = false;     // that text stands unless a later step rewrites chunks
+    bool text_done = false;     // it stood: nothing to emit after the rounds
+    bool resolved = false;      // resolve_out ran
+    int32_t rs_pre[6] = {};     // the pre-queued rounds' status (scal[0..5])
+    int64_t spec_r[2] = {0, 0};   // total chunk matches, text bytes
+    std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
 
-    // ---- anchors -> speculative guesses for chunks 1..C-1 (queued first: they do not depend on
-    //      the first step, so the GPU builds them while the host waits for it)
-    const bool dbgp = getenv("SCCG_DEBUG") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (!dbgp) return;
+    // SCCG_DEBUG: host-side phase clock (synchronises at every mark, diagnostics only)
+    void mark(const char* what) {
+        if (!walk_env().debug) return;
         (void)hipStreamSynchronize(s);
         const auto t = std::chrono::steady_clock::now();
         fprintf(stderr, "[phase]   walk.%-12s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
         t_last = t;
-    };
-    const bool walkable = nRp >= k && lastk >= 0;
-    const unsigned gsweep = grid_for(nRp - k + 1 > 0 ? nRp - k + 1 : 1, 256 * FC_PER_T) > PRESENCE_GRID
-                                ? PRESENCE_GRID : grid_for(nRp - k + 1 > 0 ? nRp - k + 1 : 1, 256 * FC_PER_T);
-    if (prepared) A.agen = g.agen;
-    else RC(queue_prepare(A, ws, s));
-
-    // ---- round 1 is queued before the host knows the first step: k_walk_init<true> resolves the
-    //      usual start on the device, and the round's status comes back with the first-step
-    //      statistics in one readback (a host round trip less).  If the first step is not the
-    //      usual one, that round is dropped and everything below runs as before.
-    // (dev_nlist: the list length is the previous round tail's pending count, scal[0])
-    auto queue_round = [&](int fbase_cap, bool dev_nlist) -> int {
-        const int32_t* nd = dev_nlist ? A.scal : nullptr;
-        PROF_LAUNCH(PROF_WALK, s, walk_kernel(A), dim3(grid_for(A.C, WWPB)), dim3(64 * WWPB), 0, s, A, (const int32_t*)A.plist,
-                    A.C, nd);
-        // a round that walks every chunk (round 1) carries nothing: a carry needs an unlisted successor
-        if (dev_nlist) RC(launch_carry(A, s));
-        hipLaunchKernelGGL(k_commit, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s, A,
-                           (const int32_t*)A.plist, A.C, nd);
-        hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
-        if (fbase_cap > 0) hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, fbase_cap), dim3(FZ_T), 0, s, A, 0);
-        SCCG_HIP(hipGetLastError());
-        RC(launch_round_end(A, 0, fbase_cap, s));
-        return 0;
-    };
-    static const bool dev_first = getenv("SCCG_HOST_FIRST_STEP") == nullptr;
-    // Round 2 usually settles every chunk (round 1 speculates, round 2 confirms): with the device
-    // first step it goes out right behind round 1 (its list length read on the device), followed by
-    // its record text when the caller resolves the text position (late_out) -- one host readback
-    // for the first step, both rounds and the text.  If round 2 left work (pending chunks, more
-    // frozen chunks, escalations) that text is simply written again after the last round.
-    static const bool spec_text_on = getenv("SCCG_NO_SPEC_TEXT") == nullptr;
-    const bool dbg_rounds = getenv("SCCG_DEBUG") != nullptr;
-    bool pre_round = false, spec_queued = false;
-    int32_t rs_pre[6] = {};
-    if (walkable && dev_first && !rt->on && !range && A.C > 0) {
-        hipLaunchKernelGGL(k_walk_init<true>, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s,
-                           A, 0, 0);
-        A.round = 1;
-        RC(queue_round(FROZEN_FIRST, false));
-        if (late_out && late_out->round1_queued && !rt->r1) {
-            rt->r1 = true;
-            RC(late_out->round1_queued(late_out->user, s));
-        }
-        A.round = 2;
-        RC(queue_round(FROZEN_FIRST, true));
-        pre_round = true;
     }
-
-    int32_t first_y = INVALID, first_p = 0, first_l = 0;
-    // ---- record text emission (k_chunk_text), queued after the rounds or speculatively (below)
-    bool resolved = false, spec_text = false, text_done = false;
-    int64_t spec_r[2] = {0, 0};   // total chunk matches, text bytes
-    auto resolve_out = [&]() -> int {
-        if (!resolved && late_out) {
-            if (rt->resolved) {
-                out = rt->out;
-            } else {
-                RC(late_out->resolve(late_out->user, &out));
-                rt->resolved = true;
-                rt->out = out;
-            }
-        }
+    // a range walk's exit when it takes no match: literal steps up to min(x_end, |T'| - k + 1)
+    int64_t literal_exit(int64_t from) const {
+        const int64_t lim = rw->x_end < (int64_t)lastk + 1 ? rw->x_end : (int64_t)lastk + 1;
+        return from < lim ? lim : from;
+    }
+    int resolve_out() {   // the caller's text position (EmitTarget::resolve is called once per call)
+        if (!resolved && late_out) RC(late_out->resolve(late_out->user, &out));
         resolved = true;
         return 0;
-    };
-    // (dev_first: the first match is the device's resolution of the usual first step, see k_chunk_text)
-    auto queue_text = [&](bool long_copy, bool dev_first) -> int {
-        const int32_t nf = dev_first ? 2 : first_y != INVALID ? 1 : 0;
-        if (A.C <= CP_MAX) {
-            hipLaunchKernelGGL(k_chunk_prefix, dim3(1), dim3(1024), 0, s, A);
-        } else {
-            const unsigned gc = grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256);
-            hipLaunchKernelGGL(k_chunk_meta, dim3(gc), dim3(256), 0, s, A);
-            RC(dev_excl_max(A.cprev, A.cprev, A.C, nullptr, A.partial, s));
-            RC(dev_excl_sum(A.flat_off, A.flat_off, A.C, A.scal64, A.partial, s));
-            RC(set_u64(reinterpret_cast<unsigned long long*>(A.scal64 + 2), {0}, s));
-        }
-        const FirstMatch F{first_y, first_p, first_l, nf};
-        hipLaunchKernelGGL(k_chunk_text<false>, dim3(grid_for(A.C, WPB)), dim3(SCCG_BLOCK), 0, s, A, F, (int)abs_p, out);
-        RC(dev_excl_sum(A.ctext, A.ctext, A.C, A.scal64 + 1, A.partial, s));
-        PROF_LAUNCH(PROF_MATCH_EMIT, s, k_chunk_text<true>, dim3(grid_for(A.C, WPB)), dim3(SCCG_BLOCK), 0, s, A, F,
-                    (int)abs_p, out);
-        if (long_copy) hipLaunchKernelGGL(k_long_copy, dim3(1024), dim3(256), 0, s, A, out);
-        SCCG_HIP(hipGetLastError());
-        return 0;
-    };
-
-    // ---- the exact first (ungated) step: first target position with any candidate
-    if (walkable && range && rw->P0 >= 0) {   // (a range walk from a gated state: no first step)
-    } else if (walkable && rt->on) {   // (a re-chunked restart: found by the first attempt)
-        first_y = rt->first_y;
-        first_p = rt->first_p;
-        first_l = rt->first_l;
-    } else if (walkable) {
-        int32_t x0 = 0;
-        unsigned long long r[9];   // fc[4..11]: first hit, first exotic, statistics of the batch's x0; fc[12]
-        if (pre_round) {
-            // the text of the usual first step needs (first_y, first_p, first_l) = the device's start
-            // resolution: known only from this readback, so the pre-queued text uses the start that
-            // k_walk_init<true> derived on the device (k_chunk_text reads it from fc)
-            if (!keep_flat && !dbg_rounds && spec_text_on) {
-                RC(resolve_out());
-                RC(queue_text(true, true));
-                spec_queued = true;
-            }
-            const RbItem it[3] = {{A.fc + 4, r, (int)sizeof r}, {A.scal, rs_pre, (int)sizeof rs_pre},
-                                  {A.scal64, spec_r, (int)sizeof spec_r}};
-            RC(dev_readback(it, 3, s));
-            if (!(r[8] != 2 && r[0] == 0 && r[4] > 0)) { pre_round = false; spec_queued = false; }   // not the usual first step: redo
-        } else {
-            const RbItem it{A.fc + 4, r, (int)sizeof r};
-            RC(dev_readback(&it, 1, s));
-        }
-        if (r[8] == 2) {   // the early sweep's statistics are not usable: the full first-step sweep
-            const unsigned g = first_sweep_grid(A);
-            hipLaunchKernelGGL(k_key0<false>, dim3(g), dim3(SCCG_BLOCK), 0, s, A, 0);
-            hipLaunchKernelGGL(k_cand_reduce, dim3(1), dim3(1024), 0, s, A, (int)g, 0);
-            SCCG_HIP(hipGetLastError());
-            const RbItem it{A.fc + 4, r, (int)sizeof r};
-            RC(dev_readback(&it, 1, s));
-        }
-        if (r[0] == 0 && r[4] > 0) {   // x0 = 0 has candidates (k_key0)
-            first_y = 0;
-            const uint64_t k0 = 1ull << 32;   // pick_key(0, -1)
-            const uint64_t pk = (r[5] >= 2 && r[6]) ? r[7] : ((r[6] && k0 < r[7]) ? k0 : r[7]);
-            first_p = (int32_t)(uint32_t)pk;
-            first_l = (int32_t)r[4];
-        }
-        while (x0 <= lastk && first_y == INVALID) {
-            const int32_t nb = (lastk - x0 + 1) < PB ? (lastk - x0 + 1) : PB;
-            RC(set_u64(A.fc + 4, {-1, -1}, s));
-            const unsigned g = gsweep;
-            PROF_LAUNCH(PROF_PRESENCE, s, k_presence, dim3(g), dim3(SCCG_BLOCK), 0, s, A, x0, nb);
-            hipLaunchKernelGGL(k_cand_reduce, dim3(1), dim3(1024), 0, s, A, (int)g, -1);
-            SCCG_HIP(hipGetLastError());
-            {
-                const RbItem it{A.fc + 4, r, (int)sizeof r};
-                RC(dev_readback(&it, 1, s));
-            }
-            if (r[0] != ~0ull && r[0] < r[1]) {
-                const int32_t y = (int32_t)r[0];
-                if (y == x0 && r[4] > 0) {   // statistics gathered by the same sweep
-                    const uint64_t k0 = 1ull << 32;   // pick_key(0, -1)
-                    const uint64_t pk = (r[5] >= 2 && r[6]) ? r[7] : ((r[6] && k0 < r[7]) ? k0 : r[7]);
-                    first_y = y;
-                    first_p = (int32_t)(uint32_t)pk;
-                    first_l = (int32_t)r[4];
-                    break;
-                }
-                if (A.k == A.kp) { first_y = y; break; }   // exact keys: y has a candidate
-                // k > KEY_K: y's first kp bases occur in R'; the exact scan decides
-                FullC f;
-                RC(run_fullc(A, y, -1, &f, s));
-                if (f.lmax > 0) { first_y = y; first_p = f.p; first_l = (int32_t)f.lmax; break; }
-                x0 = y + 1;
-                continue;
-            }
-            if (r[1] != ~0ull) {
-                FullC f;
-                RC(run_fullc(A, (int32_t)r[1], -1, &f, s));
-                if (f.lmax > 0) { first_y = (int32_t)r[1]; break; }
-                x0 = (int32_t)r[1] + 1;
-                continue;
-            }
-            x0 += nb;
-        }
-        if (first_y != INVALID && first_l == 0) {
-            FullC f;
-            RC(run_fullc(A, first_y, -1, &f, s));
-            first_p = f.p;
-            first_l = (int32_t)f.lmax;
-        }
     }
-    mark("first_step");
-    int32_t startX, startP;
-    if (range && rw->P0 >= 0) { startX = (int32_t)rw->x0; startP = (int32_t)rw->P0; }
-    else if (range && (first_y == INVALID || first_y >= rw->x_end)) {   // no match before x_end
-        rw->exit_x = literal_exit(0);
-        rw->exit_P = -1;
-        return 0;
-    } else if (first_y != INVALID) { startX = first_y + first_l; startP = first_p + first_l - 1; }
-    else { startX = lastk + 1 > 0 ? lastk + 1 : 0; startP = INVALID; }
+    int queue_round(int fbase_cap, bool dev_nlist);
+    int queue_text(bool long_copy, bool dev_first);
+    int frozen_batch(int fbase, int fcap, bool init_fy);
+    int first_step();
+    int probe_frozen_first(bool* frozen_first);
+    int run_rounds(bool frozen_first);
+    int emit_chunk_text(int64_t* out_len);
+    int emit_flat(int64_t* out_len);
+};
+int debug_round(const WalkRun& w, int64_t round, const int32_t (&rs)[6]);   // at the end of the file
 
-    // ---- init chunk state
-    const size_t C = (size_t)A.C;
-    if (!pre_round)
-        hipLaunchKernelGGL(k_walk_init<false>, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s,
-                           A, startX, startP);
+// One whole round behind the previous one: walk the listed chunks, carry, commit, the first frozen
+// batch and the round's end.  (dev_nlist: the list length is the previous round tail's pending
+// count, scal[0], read on the device)
+int WalkRun::queue_round(int fbase_cap, bool dev_nlist) {
+    const int32_t* nd = dev_nlist ? A.scal : nullptr;
+    PROF_LAUNCH(PROF_WALK, s, walk_kernel(A), dim3(grid_for(A.C, WWPB)), dim3(64 * WWPB), 0, s, A, (const int32_t*)A.plist,
+                A.C, nd);
+    // a round that walks every chunk (round 1) carries nothing: a carry needs an unlisted successor
+    if (dev_nlist) RC(launch_carry(A, s));
+    hipLaunchKernelGGL(k_commit, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s, A,
+                       (const int32_t*)A.plist, A.C, nd);
+    hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
+    if (fbase_cap > 0) hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, fbase_cap), dim3(FZ_T), 0, s, A, 0);
     SCCG_HIP(hipGetLastError());
-    // Frozen-first (host first step only): when the walk from the first match finds no window hit
-    // for FF_MIN_CHUNKS chunks (a stuck walk: T2T-like pairs), round 1 walks chunk 0 alone, the frozen
-    // chain takes the stuck stretch, and the other chunks are speculated in round 2 (k_spec_rest) --
-    // instead of speculating every chunk of the stuck stretch onto an alignment the walk never takes.
-    // The probe is k_frozen_scan on a stand-in entry (chunk 0's exit = the start state), reset after.
-    static const bool ff_env = getenv("SCCG_NO_FROZEN_FIRST") == nullptr;
-    bool frozen_first = false;
-    if (ff_env && !pre_round && !rt->on && !range && startP != INVALID && lastk >= 0 && A.C >= 2 * FF_MIN_CHUNKS) {
-        RC(dev_set_i32(A.flist, 1, {0}, s));
-        RC(dev_set_i32(A.exitX, 1, {startX}, s));
-        RC(dev_set_i32(A.exitP, 1, {startP}, s));
-        RC(dev_set_i32(A.scal + 5, 1, {1}, s));
-        RC(dev_set_i32(A.fy, 1, {INT32_MAX}, s));
-        hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, 1), dim3(FZ_T), 0, s, A, 0);
+    RC(launch_round_end(A, 0, fbase_cap, s));
+    return 0;
+}
+
+// record text emission straight from the chunks (k_chunk_text), queued after the rounds or
+// speculatively behind the pre-queued round 2
+// (dev_first: the first match is the device's resolution of the usual first step, see k_chunk_text)
+int WalkRun::queue_text(bool long_copy, bool dev_first) {
+    const int32_t nf = dev_first ? 2 : first_y != INVALID ? 1 : 0;
+    if (A.C <= CP_MAX) {
+        hipLaunchKernelGGL(k_chunk_prefix, dim3(1), dim3(1024), 0, s, A);
+    } else {
+        const unsigned gc = grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256);
+        hipLaunchKernelGGL(k_chunk_meta, dim3(gc), dim3(256), 0, s, A);
+        RC(dev_excl_max(A.cprev, A.cprev, A.C, nullptr, A.partial, s));
+        RC(dev_excl_sum(A.flat_off, A.flat_off, A.C, A.scal64, A.partial, s));
+        RC(set_u64(reinterpret_cast<unsigned long long*>(A.scal64 + 2), {0}, s));
+    }
+    const FirstMatch F{first_y, first_p, first_l, nf};
+    hipLaunchKernelGGL(k_chunk_text<false>, dim3(grid_for(A.C, WPB)), dim3(SCCG_BLOCK), 0, s, A, F, (int)abs_p, out);
+    RC(dev_excl_sum(A.ctext, A.ctext, A.C, A.scal64 + 1, A.partial, s));
+    PROF_LAUNCH(PROF_MATCH_EMIT, s, k_chunk_text<true>, dim3(grid_for(A.C, WPB)), dim3(SCCG_BLOCK), 0, s, A, F,
+                (int)abs_p, out);
+    if (long_copy) hipLaunchKernelGGL(k_long_copy, dim3(1024), dim3(256), 0, s, A, out);
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
+// frozen chunks [fbase, fbase + fcap) of the round's list (a no-op past the list), then the
+// round's end: fills and the next round's pending chunks
+int WalkRun::frozen_batch(int fbase, int fcap, bool init_fy) {
+    if (init_fy) SCCG_HIP(hipMemsetD32Async((hipDeviceptr_t)A.fy, INT32_MAX, fcap, s));
+    if (fcap > 0) hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, fcap), dim3(FZ_T), 0, s, A, fbase);
+    SCCG_HIP(hipGetLastError());
+    RC(launch_round_end(A, fbase, fcap, s));
+    return 0;
+}
+
+// The exact first (ungated) step: the first target position with any candidate -> first_y/p/l
+// (first_y stays INVALID when there is none).  With the pre-queued rounds the same readback brings
+// their status; when the first step is not the usual one they are dropped (pre_round = false) and
+// the host finds it with presence sweeps.
+int WalkRun::first_step() {
+    const int k = A.k;
+    int32_t x0 = 0;
+    unsigned long long r[9];   // fc[4..11]: first hit, first exotic, statistics of the batch's x0; fc[12]
+    if (pre_round) {
+        // the text of the usual first step needs (first_y, first_p, first_l) = the device's start
+        // resolution: known only from this readback, so the pre-queued text uses the start that
+        // k_walk_init<true> derived on the device (k_chunk_text reads it from fc)
+        if (!keep_flat && !walk_env().debug) {
+            RC(resolve_out());
+            RC(queue_text(true, true));
+            spec_queued = true;
+        }
+        const RbItem it[3] = {{A.fc + 4, r, (int)sizeof r}, {A.scal, rs_pre, (int)sizeof rs_pre},
+                              {A.scal64, spec_r, (int)sizeof spec_r}};
+        RC(dev_readback(it, 3, s));
+        if (!(r[8] != 2 && r[0] == 0 && r[4] > 0)) { pre_round = false; spec_queued = false; }   // not the usual first step: redo
+    } else {
+        const RbItem it{A.fc + 4, r, (int)sizeof r};
+        RC(dev_readback(&it, 1, s));
+    }
+    if (r[8] == 2) {   // the early sweep's statistics are not usable: the full first-step sweep
+        const unsigned g = first_sweep_grid(A);
+        hipLaunchKernelGGL(k_key0<false>, dim3(g), dim3(SCCG_BLOCK), 0, s, A, 0);
+        hipLaunchKernelGGL(k_cand_reduce, dim3(1), dim3(1024), 0, s, A, (int)g, 0);
         SCCG_HIP(hipGetLastError());
-        int32_t y0 = INT32_MAX;
+        const RbItem it{A.fc + 4, r, (int)sizeof r};
+        RC(dev_readback(&it, 1, s));
+    }
+    if (r[0] == 0 && r[4] > 0) {   // x0 = 0 has candidates (k_key0)
+        first_y = 0;
+        const uint64_t k0 = 1ull << 32;   // pick_key(0, -1)
+        const uint64_t pk = (r[5] >= 2 && r[6]) ? r[7] : ((r[6] && k0 < r[7]) ? k0 : r[7]);
+        first_p = (int32_t)(uint32_t)pk;
+        first_l = (int32_t)r[4];
+    }
+    const int64_t npos = (int64_t)A.nR - k + 1 > 0 ? (int64_t)A.nR - k + 1 : 1;
+    const unsigned gsweep = grid_for(npos, 256 * FC_PER_T) > PRESENCE_GRID ? PRESENCE_GRID : grid_for(npos, 256 * FC_PER_T);
+    while (x0 <= lastk && first_y == INVALID) {
+        const int32_t nb = (lastk - x0 + 1) < PB ? (lastk - x0 + 1) : PB;
+        RC(set_u64(A.fc + 4, {-1, -1}, s));
+        PROF_LAUNCH(PROF_PRESENCE, s, k_presence, dim3(gsweep), dim3(SCCG_BLOCK), 0, s, A, x0, nb);
+        hipLaunchKernelGGL(k_cand_reduce, dim3(1), dim3(1024), 0, s, A, (int)gsweep, -1);
+        SCCG_HIP(hipGetLastError());
         {
-            const RbItem it{A.fy, &y0, (int)sizeof y0};
+            const RbItem it{A.fc + 4, r, (int)sizeof r};
             RC(dev_readback(&it, 1, s));
         }
-        RC(dev_set_i32(A.exitX, 1, {INVALID}, s));
-        RC(dev_set_i32(A.exitP, 1, {INVALID}, s));
-        RC(dev_set_i32(A.scal + 5, 1, {0}, s));
-        frozen_first = (int64_t)y0 >= (int64_t)FF_MIN_CHUNKS * A.S;
-        if (dbgp) fprintf(stderr, "[walk] frozen-first probe: first window hit %d -> %s\n", y0, frozen_first ? "on" : "off");
-        static const bool rechunk_env = getenv("SCCG_RECHUNK") != nullptr;   // opt-in (see FF_CHUNK)
-        if (frozen_first && rechunk_env && A.S > FF_CHUNK) {
-            rt->first_y = first_y;
-            rt->first_p = first_p;
-            rt->first_l = first_l;
-            return WALK_RECHUNK;
+        if (r[0] != ~0ull && r[0] < r[1]) {
+            const int32_t y = (int32_t)r[0];
+            if (y == x0 && r[4] > 0) {   // statistics gathered by the same sweep
+                const uint64_t k0 = 1ull << 32;   // pick_key(0, -1)
+                const uint64_t pk = (r[5] >= 2 && r[6]) ? r[7] : ((r[6] && k0 < r[7]) ? k0 : r[7]);
+                first_y = y;
+                first_p = (int32_t)(uint32_t)pk;
+                first_l = (int32_t)r[4];
+                break;
+            }
+            if (A.k == A.kp) { first_y = y; break; }   // exact keys: y has a candidate
+            // k > KEY_K: y's first kp bases occur in R'; the exact scan decides
+            FullC f;
+            RC(run_fullc(A, y, -1, &f, s));
+            if (f.lmax > 0) { first_y = y; first_p = f.p; first_l = (int32_t)f.lmax; break; }
+            x0 = y + 1;
+            continue;
         }
-    }
-    if (rt->on) frozen_first = true;   // (the first attempt's probe)
-
-    if (startP != INVALID && lastk >= 0) {
-        mark("anchors");
-        int32_t nlist = frozen_first ? 1 : A.C;   // (k_walk_init listed chunk j at plist[j])
-        const bool dbg = getenv("SCCG_DEBUG") != nullptr;
-        static const bool chains_env = getenv("SCCG_NO_CHAINS") == nullptr;   // (A/B and tests)
-        bool chains_on = chains_env && !range;   // off for the rest of the call after a trapped chain
-        static const bool march_chains = [] { const char* e = getenv("SCCG_MARCH_CHAINS"); return e ? atoi(e) != 0 : true; }();
-        int march = 0;
-        int32_t prev_pend = -1;
-        A.ch_settled = 0;
-        // with the device first step, rounds 1 and 2 went out before the first readback
-        const int64_t round0 = pre_round ? 2 : 1;
-        // Rounds queued blind (SCCG_ROUND_BATCH, from round ROUND_BATCH_FROM on): once the first rounds
-        // settled the bulk, the stuck / trapped targets go on for tens of rounds with few pending
-        // chunks each, and a host readback per round costs as much as the round's kernels.  A
-        // batch queues `batch` whole rounds back to back -- every kernel takes the pending count
-        // from device memory (scal[0], written by the previous round's end; a round with nothing
-        // pending is a handful of empty launches) -- and the host reads the status once, behind the
-        // last.  Frozen chunks beyond the blind batch's FROZEN_FIRST, escalations and chains are
-        // handled after that readback exactly as after a single round: a blind round only leaves
-        // such chunks pending, so the loop's exactness argument is unchanged.
-        static const int round_batch = [] { const char* e = getenv("SCCG_ROUND_BATCH"); const int v = e ? atoi(e) : ROUND_BATCH_DEFAULT; return v >= 1 && v <= 64 ? v : ROUND_BATCH_DEFAULT; }();
-        int batch = 1;
-        for (int64_t round = round0;; round++) {
-            A.round = (int32_t)round;   // every kernel of the round gets it by value
-            const bool queued = pre_round && round == round0;
-            if (!queued) {
-                for (int b = 0; b < batch; b++) {
-                    A.round = (int32_t)(round + b);
-                    const bool dev = b > 0;   // the batch's later rounds: list length on the device
-                    const int32_t gl = dev ? A.C : nlist;
-                    PROF_LAUNCH(PROF_WALK, s, walk_kernel(A), dim3(grid_for(gl, WWPB)), dim3(64 * WWPB), 0, s, A,
-                                (const int32_t*)A.plist, gl, dev ? (const int32_t*)A.scal : (const int32_t*)nullptr);
-                    SCCG_HIP(hipGetLastError());
-                    if (dev || gl < A.C) RC(launch_carry(A, s));   // (every chunk listed: no carries)
-                    // Commit, fill the first frozen runs and find the next round's pending chunks
-                    // without waiting for the host; more frozen chunks and the rare escalated
-                    // (pn2 == 0) ones are handled after the batch's one sync.
-                    hipLaunchKernelGGL(k_commit, dim3(grid_for(gl, 256) > 4096 ? 4096 : grid_for(gl, 256)), dim3(256), 0, s, A,
-                                       (const int32_t*)A.plist, gl, dev ? (const int32_t*)A.scal : (const int32_t*)nullptr);
-                    hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
-                    if (b + 1 < batch) {   // a whole round; the last one's end is queued below
-                        hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, FROZEN_FIRST), dim3(FZ_T), 0, s, A, 0);
-                        RC(launch_round_end(A, 0, FROZEN_FIRST, s));
-                    }
-                }
-                round += batch - 1;
-                A.round = (int32_t)round;
-            }
-            res->rounds = round;
-            auto frozen_batch = [&](int fbase, int fcap, bool init_fy) -> int {   // no-op past the list
-                if (init_fy) SCCG_HIP(hipMemsetD32Async((hipDeviceptr_t)A.fy, INT32_MAX, fcap, s));
-                if (fcap > 0) hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, fcap), dim3(FZ_T), 0, s, A, fbase);
-                SCCG_HIP(hipGetLastError());
-                RC(launch_round_end(A, fbase, fcap, s));   // fills + pending
-                return 0;
-            };
-            int32_t rs[6];
-            const RbItem rs_item{A.scal, rs, (int)sizeof rs};
-            if (queued) {
-                for (int i = 0; i < 6; i++) rs[i] = rs_pre[i];
-                spec_text = spec_queued && rs[5] <= FROZEN_FIRST && rs[1] == 0;   // nothing changes after that readback
-            } else {
-                RC(frozen_batch(0, FROZEN_FIRST, false));   // fy was set by k_commit
-                RC(dev_readback(&rs_item, 1, s));
-            }
-            // A chain pays where rounds would resolve a frozen stretch hit by hit: frozen chunks still
-            // turning up from round SCCG_CHAIN_ROUND (default 10) on.  (A frozen chunk in round 1 --
-            // only chunk 0 is exact there, so the true walk froze at once -- starts one too, but only
-            // on the host-first-step path: the default device-first path queues rounds 1 and 2
-            // before its first readback and starts this loop at round 2, where round 2's frozen
-            // chunks stay with the blind batches.)  Earlier frozen chunks (N gaps of aligned pairs,
-            // short frozen stretches) stay with the blind batches.  Measured (start round 3 / 6 /
-            // 10): synthetic chr22 2.3 / 1.7 / 1.7 ms, 20 Mb T2T-like pair 5.5 / 5.7 / 5.7 ms, 100 Mb
-            // T2T-like pair 14.0 / 14.4-17.6 / 12.4 ms (23 ms without chains).
-            static const int chain_round = [] { const char* e = getenv("SCCG_CHAIN_ROUND"); const int v = e ? atoi(e) : 10; return v >= 2 ? v : 10; }();
-            // A march: chains are off (a trapped hand-back) and the rounds settle one or two chunks each
-            // -- the frontier chunk ends frozen, its frozen scan finds the next hit a chunk on, and the
-            // chunks behind it keep re-walking from entries that are not final.  A chain from the
-            // frontier (the settled frozen chunk) walks those hits on the device instead.
-            if (!chains_on && rs[0] > 0 && prev_pend >= 0 && rs[0] <= prev_pend && prev_pend - rs[0] <= 2) march++;
-            else march = 0;
-            prev_pend = rs[0];
-            static const int march_rounds = [] { const char* e = getenv("SCCG_MARCH_ROUNDS"); const int v = e ? atoi(e) : MARCH_ROUNDS; return v >= 1 ? v : MARCH_ROUNDS; }();
-            const bool march_chain = march_chains && chains_env && !range && !chains_on && march >= march_rounds && rs[5] > 0;
-            const bool chain_now = (chains_on && rs[5] > 0 && (round == 1 || round >= chain_round)) || march_chain;
-            if (chain_now) {
-                A.ch_settled = march_chain ? 1 : 0;
-                static const bool march_reset = [] { const char* e = getenv("SCCG_MARCH_RESET"); return e ? atoi(e) != 0 : false; }();
-                if (march_chain && march_reset) march = 0;
-                // a frozen chain: walk it on over the rest of the target, then the pending list again
-                int gens = 0;
-                bool trapped = false, started = true;
-                RC(run_chain(A, s, &gens, &trapped, &started));
-                static const bool keep_chains = getenv("SCCG_KEEP_CHAINS") != nullptr;   // (A/B)
-                if (trapped && !keep_chains) chains_on = false;   // a trapped walk: the rounds' re-speculation resolves it
-                if (started) {
-                    RC(frozen_batch(0, 0, false));
-                    RC(dev_readback(&rs_item, 1, s));
-                    spec_text = false;   // the chain rewrote chunks after the round's text was queued
-                    res->chains++;
-                } else {
-                    //  a march chain with no settled frozen chunk: nothing ran, so the round
-                    // takes the frozen batches past the blind one as usual and the march restarts
-                    march = 0;
-                    if (rs[5] > FROZEN_FIRST) {
-                        for (int fb = FROZEN_FIRST; fb < rs[5]; fb += FROZEN_MAX) RC(frozen_batch(fb, FROZEN_MAX, true));
-                        RC(dev_readback(&rs_item, 1, s));
-                    }
-                }
-            } else if (rs[5] > FROZEN_FIRST) {   // more frozen chunks than the blind batch covered
-                for (int fb = FROZEN_FIRST; fb < rs[5]; fb += FROZEN_MAX) RC(frozen_batch(fb, FROZEN_MAX, true));
-                RC(dev_readback(&rs_item, 1, s));
-            }
-            if (rs[1]) {
-                {   // escalations: resolve on the host, resume, commit the resumed chunks
-                    std::vector<int32_t> resumed;
-                    RC(resolve_escalations(A, s, &resumed));
-                    RC(h2d_sync(A.rlist, resumed.data(), resumed.size() * 4, s));
-                    const int32_t nr = (int32_t)resumed.size();
-                    RC(dev_set_i32(A.scal + 5, 1, {0}, s));   // frozen list of the resumed chunks
-                    hipLaunchKernelGGL(k_commit, dim3(grid_for(nr, 256) > 4096 ? 4096 : grid_for(nr, 256)), dim3(256), 0, s, A,
-                                       (const int32_t*)A.rlist, nr, (const int32_t*)nullptr);
-                    hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
-                    SCCG_HIP(hipGetLastError());
-                }
-                {
-                    const RbItem it{A.scal + 5, &rs[5], (int)sizeof(int32_t)};
-                    RC(dev_readback(&it, 1, s));
-                }
-                if (rs[5] == 0) RC(frozen_batch(0, 0, false));   // pending only
-                for (int fb = 0; fb < rs[5]; fb += FROZEN_MAX) RC(frozen_batch(fb, FROZEN_MAX, fb > 0));
-                RC(dev_readback(&rs_item, 1, s));
-            }
-            nlist = rs[0];
-            static const bool round_log = getenv("SCCG_ROUND_LOG") != nullptr;   // (determinism diagnostics)
-            if (round_log) {
-                // (with SCCG_ROUND_LOG=2 also a digest of the chunk states, to find where two runs part)
-                uint64_t hsh = 0;
-                if (getenv("SCCG_ROUND_LOG")[0] == '2') {
-                    std::vector<int32_t> v(C);
-                    const int32_t* arrs[6] = {A.exitX, A.exitP, A.usedX, A.usedP, A.cur, A.plist};
-                    for (int a = 0; a < 6; a++) {
-                        const size_t nn = a == 5 ? (size_t)(rs[0] > 0 ? rs[0] : 0) : C;
-                        SCCG_HIP(hipMemcpy(v.data(), arrs[a], nn * 4, hipMemcpyDeviceToHost));
-                        if (a == 5) std::sort(v.begin(), v.begin() + nn);
-                        for (size_t i = 0; i < nn; i++) hsh = (hsh ^ (uint32_t)v[i]) * 0x100000001b3ull + a;
-                    }
-                }
-                fprintf(stderr, "[round] %lld pending %d esc %d frozen %d chains %lld digest %016llx\n", (long long)round, rs[0], rs[1],
-                        rs[5], (long long)res->chains, (unsigned long long)hsh);
-            }
-            if (dbg) {
-                SCCG_HIP(hipStreamSynchronize(s));
-                static thread_local auto tprev = std::chrono::steady_clock::now();
-                const auto tnow = std::chrono::steady_clock::now();
-                fprintf(stderr, "[walk] round %lld: %d walked, %.3f ms since last mark\n", (long long)round, nlist,
-                        std::chrono::duration<double, std::milli>(tnow - tprev).count());
-                tprev = tnow;
-            }
-            static const bool dbg_all = getenv("SCCG_DEBUG_ALLROUNDS") != nullptr;
-            if (dbg && (round <= 2 || dbg_all)) {   // per-chunk cost profile of the rounds' walked chunks
-                constexpr size_t DS = DBG_SLOTS;
-                std::vector<uint64_t> d(C * DS);
-                SCCG_HIP(hipMemcpyAsync(d.data(), A.dbg, C * DS * 8, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipStreamSynchronize(s));
-                std::vector<uint64_t> tk(C);
-                uint64_t sum[14] = {};
-                const int64_t rep = A.dbg_round > 0 ? A.dbg_round : round;   // (the round whose counters are kept)
-                for (size_t j = 0; j < C; j++) {
-                    const bool mine = d[j * DS + 14] == (uint64_t)rep;
-                    tk[j] = mine ? d[j * DS] : 0;
-                    if (mine) for (int i = 0; i < 14; i++) sum[i] += d[j * DS + i];
-                }
-                std::vector<uint64_t> sorted = tk;
-                std::sort(sorted.begin(), sorted.end());
-                {
-                    int dev = 0, khz = 0;
-                    (void)hipGetDevice(&dev);
-                    (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev);
-                    fprintf(stderr, "[walk] wall clock rate %d kHz\n", khz);
-                }
-                fprintf(stderr, "[walk] r%lld chunk ticks(10ns): mean %.0f p50 %llu p90 %llu p99 %llu max %llu | totals: matches %llu "
-                        "batches %llu wides %llu windows %llu cands %llu extbases %llu\n",
-                        (long long)round, (double)sum[0] / C, (unsigned long long)sorted[C / 2], (unsigned long long)sorted[C * 9 / 10],
-                        (unsigned long long)sorted[C * 99 / 100], (unsigned long long)sorted[C - 1],
-                        (unsigned long long)sum[1], (unsigned long long)sum[2], (unsigned long long)sum[3],
-                        (unsigned long long)sum[4], (unsigned long long)sum[5], (unsigned long long)sum[6]);
-                {   // launch spread: when the chunks' waves started and ended, from the first start
-                    uint64_t s0 = ~0ull;
-                    for (size_t j = 0; j < C; j++) if (d[j * DS + 14] == (uint64_t)rep && d[j * DS + 15] < s0) s0 = d[j * DS + 15];
-                    std::vector<uint64_t> st, en;
-                    for (size_t j = 0; j < C; j++)
-                        if (d[j * DS + 14] == (uint64_t)rep) { st.push_back(d[j * DS + 15] - s0); en.push_back(d[j * DS + 15] - s0 + d[j * DS]); }
-                    if (!st.empty()) {
-                        std::sort(st.begin(), st.end());
-                        std::sort(en.begin(), en.end());
-                        const size_t m = st.size();
-                        fprintf(stderr, "[walk] r%lld %zu waves: start p50 %llu p90 %llu max %llu | end p50 %llu p90 %llu p99 %llu max %llu (10ns)\n",
-                                (long long)round, m, (unsigned long long)st[m / 2], (unsigned long long)st[m * 9 / 10],
-                                (unsigned long long)st[m - 1], (unsigned long long)en[m / 2], (unsigned long long)en[m * 9 / 10],
-                                (unsigned long long)en[m * 99 / 100], (unsigned long long)en[m - 1]);
-                    }
-                }
-                fprintf(stderr, "[walk] r1 step phases (10ns, summed over chunks): window %llu find %llu cand+lce %llu tail %llu "
-                        "hash %llu wide %llu (wide positions %llu)\n",
-                        (unsigned long long)sum[7], (unsigned long long)sum[8], (unsigned long long)sum[9], (unsigned long long)sum[10],
-                        (unsigned long long)sum[11], (unsigned long long)sum[12], (unsigned long long)sum[13]);
-                std::vector<size_t> idx(C);
-                for (size_t j = 0; j < C; j++) idx[j] = j;
-                const size_t nshow = C < 5 ? C : 5;
-                std::partial_sort(idx.begin(), idx.begin() + nshow, idx.end(), [&](size_t a, size_t b) { return tk[a] > tk[b]; });
-                for (size_t q = 0; q < nshow; q++) {
-                    const uint64_t* e = &d[idx[q] * DS];
-                    fprintf(stderr, "   slow chunk %zu: ticks %llu matches %llu batches %llu wides %llu windows %llu cands %llu ext %llu "
-                            "| win %llu find %llu cand %llu tail %llu hash %llu wide %llu widepos %llu\n",
-                            idx[q], (unsigned long long)e[0], (unsigned long long)e[1], (unsigned long long)e[2],
-                            (unsigned long long)e[3], (unsigned long long)e[4], (unsigned long long)e[5], (unsigned long long)e[6],
-                            (unsigned long long)e[7], (unsigned long long)e[8], (unsigned long long)e[9], (unsigned long long)e[10],
-                            (unsigned long long)e[11], (unsigned long long)e[12], (unsigned long long)e[13]);
-                }
-            }
-            static const int dbg_chunk = getenv("SCCG_DEBUG_CHUNK") ? atoi(getenv("SCCG_DEBUG_CHUNK")) : -1;
-            if (dbg && dbg_chunk >= 0 && dbg_chunk < A.C) {   // both trajectory buffers of one chunk
-                const size_t j = (size_t)dbg_chunk;
-                int32_t cur = 0, cn[2] = {0, 0}, ux = 0, up = 0, ex = 0, ep = 0, sq = 0;
-                SCCG_HIP(hipMemcpy(&cur, A.cur + j, 4, hipMemcpyDeviceToHost));
-                SCCG_HIP(hipMemcpy(&cn[0], A.cnt[0] + j, 4, hipMemcpyDeviceToHost));
-                SCCG_HIP(hipMemcpy(&cn[1], A.cnt[1] + j, 4, hipMemcpyDeviceToHost));
-                SCCG_HIP(hipMemcpy(&ux, A.usedX + j, 4, hipMemcpyDeviceToHost));
-                SCCG_HIP(hipMemcpy(&up, A.usedP + j, 4, hipMemcpyDeviceToHost));
-                SCCG_HIP(hipMemcpy(&ex, A.exitX + j, 4, hipMemcpyDeviceToHost));
-                SCCG_HIP(hipMemcpy(&ep, A.exitP + j, 4, hipMemcpyDeviceToHost));
-                SCCG_HIP(hipMemcpy(&sq, A.seedq + j, 4, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[chunk %zu] round %lld cur=%d used=(%d,%d) exit=(%d,%d) seedq=%d\n", j, (long long)round, cur, ux,
-                        up, ex, ep, sq);
-                for (int b = 0; b < 2; b++) {
-                    const int n = cn[b] < 80 ? cn[b] : 80;
-                    std::vector<int32_t> tt(n > 0 ? n : 1), pp(tt.size()), ll(tt.size());
-                    if (n > 0) {
-                        SCCG_HIP(hipMemcpy(tt.data(), A.bt[b] + j * A.cap, n * 4, hipMemcpyDeviceToHost));
-                        SCCG_HIP(hipMemcpy(pp.data(), A.bp[b] + j * A.cap, n * 4, hipMemcpyDeviceToHost));
-                        SCCG_HIP(hipMemcpy(ll.data(), A.bl[b] + j * A.cap, n * 4, hipMemcpyDeviceToHost));
-                    }
-                    fprintf(stderr, "  buf%d (%d):", b, cn[b]);
-                    for (int q = 0; q < n; q++) fprintf(stderr, " (%d,%d,%d)", tt[q], pp[q], ll[q]);
-                    fprintf(stderr, "\n");
-                }
-            }
-            static const int dbg_rounds = getenv("SCCG_DEBUG_ROUNDS") ? atoi(getenv("SCCG_DEBUG_ROUNDS")) : 3;
-            if (dbg && (round <= dbg_rounds || round % 1000 == 0)) {
-                std::vector<int32_t> g(C), ex(C), ep(C), ux(C), up(C), cur(C), c0(C), c1(C);
-                SCCG_HIP(hipMemcpyAsync(g.data(), A.guess, C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipMemcpyAsync(ex.data(), A.exitX, C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipMemcpyAsync(ep.data(), A.exitP, C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipMemcpyAsync(ux.data(), A.usedX, C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipMemcpyAsync(up.data(), A.usedP, C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipMemcpyAsync(cur.data(), A.cur, C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipMemcpyAsync(c0.data(), A.cnt[0], C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipMemcpyAsync(c1.data(), A.cnt[1], C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipStreamSynchronize(s));
-                size_t ginv = 0, einv = 0, settled = 0;
-                for (size_t j = 0; j < C; j++) {
-                    ginv += g[j] == INVALID;
-                    einv += ex[j] == INVALID;
-                    const int32_t px = j ? ex[j - 1] : startX, pp = j ? ep[j - 1] : startP;
-                    settled += (px == ux[j] && pp == up[j]);
-                }
-                fprintf(stderr, "[walk] round %lld launched %d: guess INVALID %zu, exit INVALID %zu, settled %zu/%zu\n",
-                        (long long)round, nlist, ginv, einv, settled, C);
-                std::vector<int32_t> stt(C);
-                SCCG_HIP(hipMemcpyAsync(stt.data(), A.status, C * 4, hipMemcpyDeviceToHost, s));
-                SCCG_HIP(hipStreamSynchronize(s));
-                int shown = 0;
-                for (size_t j = 1; j < C && shown < 6; j++) {
-                    if (ex[j - 1] == ux[j] && ep[j - 1] == up[j]) continue;
-                    shown++;
-                    fprintf(stderr, "  unsettled %zu lo=%d guess=%d used=(%d,%d) pred_exit=(%d,%d) exit=(%d,%d) st=%d cur=%d cnt=%d/%d\n",
-                            j, (int)(j * A.S), g[j], ux[j], up[j], ex[j - 1], ep[j - 1], ex[j], ep[j], stt[j], cur[j], c0[j], c1[j]);
-                    const int32_t b = cur[j];
-                    const int32_t nshow = (b ? c1[j] : c0[j]) < 4 ? (b ? c1[j] : c0[j]) : 4;
-                    std::vector<int32_t> tt(4), pp(4), ll(4);
-                    SCCG_HIP(hipMemcpyAsync(tt.data(), A.bt[b] + j * A.cap, 16, hipMemcpyDeviceToHost, s));
-                    SCCG_HIP(hipMemcpyAsync(pp.data(), A.bp[b] + j * A.cap, 16, hipMemcpyDeviceToHost, s));
-                    SCCG_HIP(hipMemcpyAsync(ll.data(), A.bl[b] + j * A.cap, 16, hipMemcpyDeviceToHost, s));
-                    SCCG_HIP(hipStreamSynchronize(s));
-                    for (int q = 0; q < nshow; q++) fprintf(stderr, "      m%d (%d,%d,%d)\n", q, tt[q], pp[q], ll[q]);
-                }
-            }
-            if (frozen_first && round == 1) {   // first speculation of every chunk still never walked
-                hipLaunchKernelGGL(k_spec_rest, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s, A);
-                SCCG_HIP(hipGetLastError());
-                const RbItem it{A.scal, &nlist, (int)sizeof nlist};
-                RC(dev_readback(&it, 1, s));
-            }
-            if (round == 2 && spec_text && nlist == 0) text_done = true;
-            if (!nlist) break;
-            // the next iteration's batch: blind rounds once past the first ones, unless this round
-            // left work only the host resolves (escalations, a chain about to start)
-            batch = (round + 1 >= ROUND_BATCH_FROM && !rs[1]) ? round_batch : 1;
-            if (round > 4 * (int64_t)A.C + 16) return SCCG_E_INTERNAL;
-            if (late_out && late_out->abandon && late_out->abandon(late_out->user)) return WALK_ABANDONED;
+        if (r[1] != ~0ull) {
+            FullC f;
+            RC(run_fullc(A, (int32_t)r[1], -1, &f, s));
+            if (f.lmax > 0) { first_y = (int32_t)r[1]; break; }
+            x0 = (int32_t)r[1] + 1;
+            continue;
         }
+        x0 += nb;
     }
+    if (first_y != INVALID && first_l == 0) {
+        FullC f;
+        RC(run_fullc(A, first_y, -1, &f, s));
+        first_p = f.p;
+        first_l = (int32_t)f.lmax;
+    }
+    return 0;
+}
 
-    mark("rounds");
-    const int32_t nfirst = first_y != INVALID ? 1 : 0;
-    if (!keep_flat) {
-        // ---- record text straight from the chunks (k_chunk_text): no flattened match list
-        RC(resolve_out());   // the caller's text position is known now
-        int64_t text = 0, nmc = 0;
-        if (startP != INVALID && lastk >= 0) {
-            if (!text_done) {   // (else round 2's speculative text, long copies included, stands)
-                RC(queue_text(true, false));
-                const RbItem it{A.scal64, spec_r, (int)sizeof spec_r};
-                RC(dev_readback(&it, 1, s));
-            }
-            nmc = spec_r[0];
-            text = spec_r[1];
-        } else if (nTp > 0) {   // no first match: the whole target is one literal
-            hipLaunchKernelGGL(k_copy, dim3(grid_for(nTp, WPB * LONG_PIECE)), dim3(SCCG_BLOCK), 0, s, Tp, nTp, out);
+// Frozen-first (host first step only): when the walk from the first match finds no window hit
+// for FF_MIN_CHUNKS chunks (a stuck walk: T2T-like pairs), round 1 walks chunk 0 alone, the frozen
+// chain takes the stuck stretch, and the other chunks are speculated in round 2 (k_spec_rest) --
+// instead of speculating every chunk of the stuck stretch onto an alignment the walk never takes.
+// The probe is k_frozen_scan on a stand-in entry (chunk 0's exit = the start state), reset after.
+int WalkRun::probe_frozen_first(bool* frozen_first) {
+    RC(dev_set_i32(A.flist, 1, {0}, s));
+    RC(dev_set_i32(A.exitX, 1, {startX}, s));
+    RC(dev_set_i32(A.exitP, 1, {startP}, s));
+    RC(dev_set_i32(A.scal + 5, 1, {1}, s));
+    RC(dev_set_i32(A.fy, 1, {INT32_MAX}, s));
+    hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, 1), dim3(FZ_T), 0, s, A, 0);
+    SCCG_HIP(hipGetLastError());
+    int32_t y0 = INT32_MAX;
+    {
+        const RbItem it{A.fy, &y0, (int)sizeof y0};
+        RC(dev_readback(&it, 1, s));
+    }
+    RC(dev_set_i32(A.exitX, 1, {INVALID}, s));
+    RC(dev_set_i32(A.exitP, 1, {INVALID}, s));
+    RC(dev_set_i32(A.scal + 5, 1, {0}, s));
+    *frozen_first = (int64_t)y0 >= (int64_t)FF_MIN_CHUNKS * A.S;
+    if (walk_env().debug)
+        fprintf(stderr, "[walk] frozen-first probe: first window hit %d -> %s\n", y0, *frozen_first ? "on" : "off");
+    return 0;
+}
+
+// The rounds: walk the pending chunks, commit, resolve frozen chunks, escalations and chains,
+// until no chunk is pending.  One host readback per round (the pre-queued rounds 1 and 2: the
+// first step's).
+int WalkRun::run_rounds(bool frozen_first) {
+    const bool range = rw != nullptr;
+    int32_t nlist = frozen_first ? 1 : A.C;   // (k_walk_init listed chunk j at plist[j])
+    bool chains_on = !range;   // off for the rest of the call after a trapped chain
+    int march = 0;
+    int32_t prev_pend = -1;
+    A.ch_settled = 0;
+    // with the device first step, rounds 1 and 2 went out before the first readback
+    const int64_t round0 = pre_round ? 2 : 1;
+    for (int64_t round = round0;; round++) {
+        A.round = (int32_t)round;   // every kernel of the round gets it by value
+        const bool queued = pre_round && round == round0;
+        if (!queued) {
+            PROF_LAUNCH(PROF_WALK, s, walk_kernel(A), dim3(grid_for(nlist, WWPB)), dim3(64 * WWPB), 0, s, A,
+                        (const int32_t*)A.plist, nlist, (const int32_t*)nullptr);
             SCCG_HIP(hipGetLastError());
-            text = nTp;
+            if (nlist < A.C) RC(launch_carry(A, s));   // (every chunk listed: no carries)
+            // Commit, fill the first frozen runs and find the next round's pending chunks without
+            // waiting for the host; more frozen chunks and the rare escalated (pn2 == 0) ones are
+            // handled after the round's sync.
+            hipLaunchKernelGGL(k_commit, dim3(grid_for(nlist, 256) > 4096 ? 4096 : grid_for(nlist, 256)), dim3(256), 0, s, A,
+                               (const int32_t*)A.plist, nlist, (const int32_t*)nullptr);
+            hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
         }
-        res->n_matches = nmc + nfirst;
-        g_last_n = 0;
-        *out_len = text;
-        mark("emit");
-        return 0;
+        res->rounds = round;
+        int32_t rs[6];
+        const RbItem rs_item{A.scal, rs, (int)sizeof rs};
+        if (queued) {
+            for (int i = 0; i < 6; i++) rs[i] = rs_pre[i];
+            spec_text = spec_queued && rs[5] <= FROZEN_FIRST && rs[1] == 0;   // nothing changes after that readback
+        } else {
+            RC(frozen_batch(0, FROZEN_FIRST, false));   // fy was set by k_commit
+            RC(dev_readback(&rs_item, 1, s));
+        }
+        // A chain pays where rounds would resolve a frozen stretch hit by hit: frozen chunks still
+        // turning up from round CHAIN_ROUND on.  (A frozen chunk in round 1 -- only chunk 0 is exact
+        // there, so the true walk froze at once -- starts one too, but only on the host-first-step
+        // path: the device-first path queues rounds 1 and 2 before its first readback and starts
+        // this loop at round 2.)  Earlier frozen chunks (N gaps of aligned pairs, short frozen
+        // stretches) stay with the rounds.  Measured (start round 3 / 6 / 10): synthetic chr22
+        // 2.3 / 1.7 / 1.7 ms, 20 Mb T2T-like pair 5.5 / 5.7 / 5.7 ms, 100 Mb T2T-like pair
+        // 14.0 / 14.4-17.6 / 12.4 ms (23 ms without chains).
+        // A march: chains are off (a trapped hand-back) and the rounds settle one or two chunks each
+        // -- the frontier chunk ends frozen, its frozen scan finds the next hit a chunk on, and the
+        // chunks behind it keep re-walking from entries that are not final.  A chain from the
+        // frontier (the settled frozen chunk) walks those hits on the device instead.
+        if (!chains_on && rs[0] > 0 && prev_pend >= 0 && rs[0] <= prev_pend && prev_pend - rs[0] <= 2) march++;
+        else march = 0;
+        prev_pend = rs[0];
+        const bool march_chain = !range && !chains_on && march >= MARCH_ROUNDS && rs[5] > 0;
+        const bool chain_now = (chains_on && rs[5] > 0 && (round == 1 || round >= CHAIN_ROUND)) || march_chain;
+        if (chain_now) {
+            A.ch_settled = march_chain ? 1 : 0;
+            // a frozen chain: walk it on over the rest of the target, then the pending list again
+            int gens = 0;
+            bool trapped = false, started = true;
+            RC(run_chain(A, s, &gens, &trapped, &started));
+            if (trapped) chains_on = false;   // a trapped walk: the rounds' re-speculation resolves it
+            if (started) {
+                RC(frozen_batch(0, 0, false));
+                RC(dev_readback(&rs_item, 1, s));
+                spec_text = false;   // the chain rewrote chunks after the round's text was queued
+                res->chains++;
+            } else {
+                // a march chain with no settled frozen chunk: nothing ran, so the round takes the
+                // frozen batches past the first one as usual and the march restarts
+                march = 0;
+                if (rs[5] > FROZEN_FIRST) {
+                    for (int fb = FROZEN_FIRST; fb < rs[5]; fb += FROZEN_MAX) RC(frozen_batch(fb, FROZEN_MAX, true));
+                    RC(dev_readback(&rs_item, 1, s));
+                }
+            }
+        } else if (rs[5] > FROZEN_FIRST) {   // more frozen chunks than the first batch covered
+            for (int fb = FROZEN_FIRST; fb < rs[5]; fb += FROZEN_MAX) RC(frozen_batch(fb, FROZEN_MAX, true));
+            RC(dev_readback(&rs_item, 1, s));
+        }
+        if (rs[1]) {
+            {   // escalations: resolve on the host, resume, commit the resumed chunks
+                std::vector<int32_t> resumed;
+                RC(resolve_escalations(A, s, &resumed));
+                RC(h2d_sync(A.rlist, resumed.data(), resumed.size() * 4, s));
+                const int32_t nr = (int32_t)resumed.size();
+                RC(dev_set_i32(A.scal + 5, 1, {0}, s));   // frozen list of the resumed chunks
+                hipLaunchKernelGGL(k_commit, dim3(grid_for(nr, 256) > 4096 ? 4096 : grid_for(nr, 256)), dim3(256), 0, s, A,
+                                   (const int32_t*)A.rlist, nr, (const int32_t*)nullptr);
+                hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
+                SCCG_HIP(hipGetLastError());
+            }
+            {
+                const RbItem it{A.scal + 5, &rs[5], (int)sizeof(int32_t)};
+                RC(dev_readback(&it, 1, s));
+            }
+            if (rs[5] == 0) RC(frozen_batch(0, 0, false));   // pending only
+            for (int fb = 0; fb < rs[5]; fb += FROZEN_MAX) RC(frozen_batch(fb, FROZEN_MAX, fb > 0));
+            RC(dev_readback(&rs_item, 1, s));
+        }
+        nlist = rs[0];
+        RC(debug_round(*this, round, rs));
+        if (frozen_first && round == 1) {   // first speculation of every chunk still never walked
+            hipLaunchKernelGGL(k_spec_rest, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s, A);
+            SCCG_HIP(hipGetLastError());
+            const RbItem it{A.scal, &nlist, (int)sizeof nlist};
+            RC(dev_readback(&it, 1, s));
+        }
+        if (round == 2 && spec_text && nlist == 0) text_done = true;
+        if (!nlist) return 0;
+        if (round > 4 * (int64_t)A.C + 16) return SCCG_E_INTERNAL;
+        if (late_out && late_out->abandon && late_out->abandon(late_out->user)) return WALK_ABANDONED;
     }
-    // ---- flatten: first match, then every chunk's trajectory
+}
+
+// the record text straight from the chunks (k_chunk_text): no flattened match list
+int WalkRun::emit_chunk_text(int64_t* out_len) {
+    RC(resolve_out());   // the caller's text position is known now
+    int64_t text = 0, nmc = 0;
+    if (startP != INVALID && lastk >= 0) {
+        if (!text_done) {   // (else round 2's speculative text, long copies included, stands)
+            RC(queue_text(true, false));
+            const RbItem it{A.scal64, spec_r, (int)sizeof spec_r};
+            RC(dev_readback(&it, 1, s));
+        }
+        nmc = spec_r[0];
+        text = spec_r[1];
+    } else if (nTp > 0) {   // no first match: the whole target is one literal
+        hipLaunchKernelGGL(k_copy, dim3(grid_for(nTp, WPB * LONG_PIECE)), dim3(SCCG_BLOCK), 0, s, Tp, nTp, out);
+        SCCG_HIP(hipGetLastError());
+        text = nTp;
+    }
+    res->n_matches = nmc + (first_y != INVALID ? 1 : 0);
+    g_last_n = 0;
+    *out_len = text;
+    mark("emit");
+    return 0;
+}
+
+// the flattened match list (first match, then every chunk's trajectory; global_matches), a range
+// walk's exit state, or the record text written from that list
+int WalkRun::emit_flat(int64_t* out_len) {
+    const int32_t nfirst = first_y != INVALID ? 1 : 0;
     hipLaunchKernelGGL(k_chunk_counts, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s, A);
     RC(dev_excl_sum(A.flat_off, A.flat_off, A.C, A.scal64, A.partial, s));
     if (nfirst) {
@@ -3865,7 +3339,7 @@ int match_and_emit_impl(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64
     res->n_matches = nm;
     g_last = A;
     g_last_n = nm;
-    if (range) {   // the exit state: the last chunk's (its walk ends at the first index >= x_end)
+    if (rw) {   // the exit state: the last chunk's (its walk ends at the first index >= x_end)
         int32_t ex[2];
         const RbItem it[2] = {{A.exitX + (A.C - 1), &ex[0], 4}, {A.exitP + (A.C - 1), &ex[1], 4}};
         RC(dev_readback(it, 2, s));
@@ -3903,19 +3377,107 @@ int match_and_emit_impl(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64
     return 0;
 }
 
+// The walk driver: preparation (unless global_prepare queued it), rounds 1 and 2 queued blind
+// behind it, the exact first step, the rounds, the record text.
+int match_and_emit_impl(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nTp, int k, int m, int chunk,
+                        void* ws, size_t ws_bytes, uint8_t* out, int64_t* out_len, WalkResult* res, hipStream_t s,
+                        bool abs_p, const EmitTarget* late_out, bool keep_flat, RangeWalk* rw = nullptr) {
+    if (m < 0 || 2 * m + 1 > WCAP || k > KMAX || k < 1) return SCCG_E_UNSUPPORTED;
+    const bool range = rw != nullptr;
+    if (range && (rw->x0 < 0 || rw->P0 < -1 || (rw->P0 == -1 && rw->x0 != 0) || rw->x0 > nTp || rw->P0 >= nRp))
+        return SCCG_E_UNSUPPORTED;
+    const Prepared g = g_prep;   // queued by global_prepare (the caller ordered s after it)
+    g_prep = Prepared{};
+    const bool prepared = g.ws == ws && g.R == Rp && g.T == Tp && g.nR == nRp && g.nT == nTp && g.k == k && g.m == m &&
+                          g.chunk == chunk;
+    size_t used = 0;
+    const int32_t lastk = (int32_t)nTp - k;
+    WalkRun w{make_ptrs(Rp, nRp, Tp, nTp, k, m, chunk, ws, ws_bytes, &used, prepared ? g.abits : 0),
+              s, res, late_out, rw, out, abs_p, keep_flat, Tp, nTp, lastk};
+    if (used > ws_bytes) return SCCG_E_INTERNAL;
+    WalkPtrs& A = w.A;
+    res->rounds = 0;
+    res->chains = 0;
+    res->n_matches = 0;
+    if (range) {
+        const int64_t xe = rw->x_end < nTp ? rw->x_end : nTp;
+        A.xlo = (int32_t)rw->x0;
+        A.xhi = (int32_t)(xe > rw->x0 ? xe : rw->x0);
+        A.C = (int32_t)(((int64_t)A.xhi - A.xlo + chunk - 1) / chunk);
+        if (A.C < 1) A.C = 1;
+        g_last_n = 0;
+        if (nRp < k || lastk < 0) {   // no k-mer to probe: every step is a literal
+            rw->exit_x = w.literal_exit(rw->x0);
+            rw->exit_P = rw->P0;
+            return 0;
+        }
+    }
+    res->chunks = A.C;
+
+    // ---- anchors -> speculative guesses for chunks 1..C-1 (queued first: they do not depend on
+    //      the first step, so the GPU builds them while the host waits for it)
+    const bool walkable = nRp >= k && lastk >= 0;
+    if (prepared) A.agen = g.agen;
+    else RC(queue_prepare(A, ws, s));
+
+    // ---- round 1 is queued before the host knows the first step: k_walk_init<true> resolves the
+    //      usual start on the device, and the round's status comes back with the first-step
+    //      statistics in one readback (a host round trip less).  Round 2 usually settles every
+    //      chunk (round 1 speculates, round 2 confirms), so it goes out right behind round 1 (its
+    //      list length read on the device), followed by its record text when the caller resolves
+    //      the text position (first_step) -- one host readback for the first step, both rounds and
+    //      the text.  If the first step is not the usual one, both rounds are dropped; if round 2
+    //      left work (pending chunks, more frozen chunks, escalations) that text is simply written
+    //      again after the last round.  (Not for a range walk, whose start is the caller's.)
+    if (walkable && !range && A.C > 0) {
+        hipLaunchKernelGGL(k_walk_init<true>, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s,
+                           A, 0, 0);
+        A.round = 1;
+        RC(w.queue_round(FROZEN_FIRST, false));
+        if (late_out && late_out->round1_queued) RC(late_out->round1_queued(late_out->user, s));
+        A.round = 2;
+        RC(w.queue_round(FROZEN_FIRST, true));
+        w.pre_round = true;
+    }
+
+    // ---- the exact first step (a range walk from a gated state has none) and the start state
+    if (walkable && !(range && rw->P0 >= 0)) RC(w.first_step());
+    w.mark("first_step");
+    if (range && rw->P0 >= 0) { w.startX = (int32_t)rw->x0; w.startP = (int32_t)rw->P0; }
+    else if (range && (w.first_y == INVALID || w.first_y >= rw->x_end)) {   // no match before x_end
+        rw->exit_x = w.literal_exit(0);
+        rw->exit_P = -1;
+        return 0;
+    } else if (w.first_y != INVALID) { w.startX = w.first_y + w.first_l; w.startP = w.first_p + w.first_l - 1; }
+    else { w.startX = lastk + 1 > 0 ? lastk + 1 : 0; w.startP = INVALID; }
+
+    // ---- init chunk state (the pre-queued rounds did it on the device)
+    if (!w.pre_round)
+        hipLaunchKernelGGL(k_walk_init<false>, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s,
+                           A, w.startX, w.startP);
+    SCCG_HIP(hipGetLastError());
+    bool frozen_first = false;
+    if (!w.pre_round && !range && w.startP != INVALID && lastk >= 0 && A.C >= 2 * FF_MIN_CHUNKS)
+        RC(w.probe_frozen_first(&frozen_first));
+
+    if (w.startP != INVALID && lastk >= 0) {
+        w.mark("anchors");
+        RC(w.run_rounds(frozen_first));
+    }
+    w.mark("rounds");
+    return keep_flat ? w.emit_flat(out_len) : w.emit_chunk_text(out_len);
+}
+
 }  // namespace
 
 int global_walk_range(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nTp, int k, int m, int chunk, void* ws,
                       size_t ws_bytes, int64_t x0, int64_t P0, int64_t x_end, int64_t* exit_x, int64_t* exit_P,
                       WalkResult* res, hipStream_t s) {
     global_prepare_reset();
-    Rechunk rt;
     RangeWalk rw;
     rw.x0 = x0; rw.P0 = P0; rw.x_end = x_end;
     int64_t tl = 0;
-    const int rc = match_and_emit_impl(Rp, nRp, Tp, nTp, k, m, chunk, ws, ws_bytes, nullptr, &tl, res, s, false, nullptr,
-                                       true, &rt, &rw);
-    if (rc) return rc;
+    RC(match_and_emit_impl(Rp, nRp, Tp, nTp, k, m, chunk, ws, ws_bytes, nullptr, &tl, res, s, false, nullptr, true, &rw));
     *exit_x = rw.exit_x;
     *exit_P = rw.exit_P;
     return 0;
@@ -3924,14 +3486,7 @@ int global_walk_range(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t
 int global_match_and_emit(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nTp, int k, int m, int chunk,
                           void* ws, size_t ws_bytes, uint8_t* out, int64_t* out_len, WalkResult* res, hipStream_t s,
                           bool abs_p, const EmitTarget* late_out, bool keep_flat) {
-    Rechunk rt;
-    const int rc = match_and_emit_impl(Rp, nRp, Tp, nTp, k, m, chunk, ws, ws_bytes, out, out_len, res, s, abs_p, late_out,
-                                       keep_flat, &rt);
-    if (rc != WALK_RECHUNK) return rc;
-    if (walk_workspace_bytes(nRp, nTp, k, FF_CHUNK) > ws_bytes) return SCCG_E_INTERNAL;
-    rt.on = true;
-    return match_and_emit_impl(Rp, nRp, Tp, nTp, k, m, FF_CHUNK, ws, ws_bytes, out, out_len, res, s, abs_p, late_out,
-                               keep_flat, &rt);
+    return match_and_emit_impl(Rp, nRp, Tp, nTp, k, m, chunk, ws, ws_bytes, out, out_len, res, s, abs_p, late_out, keep_flat);
 }
 
 // a workspace buffer is about to be freed: its anchor table's generations are gone with it
@@ -3939,3 +3494,171 @@ void walk_forget_workspace(const void* ws) {
     std::lock_guard<std::mutex> lk(g_anchor_mu);
     g_anchor_seen.erase(ws);
 }
+
+// Everything a diagnostic run prints after a round (walk_env(): SCCG_ROUND_LOG, SCCG_DEBUG and its
+// companions), after the round's last readback: rs is the round's status, nlist the next round's
+// pending count.  A run without those variables returns at once.
+namespace {
+int debug_round(const WalkRun& w, int64_t round, const int32_t (&rs)[6]) {
+    const WalkEnv& env = walk_env();
+    if (!env.round_log && !env.debug) return 0;
+    const WalkPtrs& A = w.A;
+    hipStream_t s = w.s;
+    const WalkResult* res = w.res;
+    const size_t C = (size_t)A.C;
+    const int32_t nlist = rs[0], startX = w.startX, startP = w.startP;
+    const bool dbg = env.debug;
+    if (env.round_log) {   // (determinism diagnostics)
+        // (with SCCG_ROUND_LOG=2 also a digest of the chunk states, to find where two runs part)
+        uint64_t hsh = 0;
+        if (env.round_log == 2) {
+            std::vector<int32_t> v(C);
+            const int32_t* arrs[6] = {A.exitX, A.exitP, A.usedX, A.usedP, A.cur, A.plist};
+            for (int a = 0; a < 6; a++) {
+                const size_t nn = a == 5 ? (size_t)(rs[0] > 0 ? rs[0] : 0) : C;
+                SCCG_HIP(hipMemcpy(v.data(), arrs[a], nn * 4, hipMemcpyDeviceToHost));
+                if (a == 5) std::sort(v.begin(), v.begin() + nn);
+                for (size_t i = 0; i < nn; i++) hsh = (hsh ^ (uint32_t)v[i]) * 0x100000001b3ull + a;
+            }
+        }
+        fprintf(stderr, "[round] %lld pending %d esc %d frozen %d chains %lld digest %016llx\n", (long long)round, rs[0], rs[1],
+                rs[5], (long long)res->chains, (unsigned long long)hsh);
+    }
+    if (dbg) {
+        SCCG_HIP(hipStreamSynchronize(s));
+        static thread_local auto tprev = std::chrono::steady_clock::now();
+        const auto tnow = std::chrono::steady_clock::now();
+        fprintf(stderr, "[walk] round %lld: %d walked, %.3f ms since last mark\n", (long long)round, nlist,
+                std::chrono::duration<double, std::milli>(tnow - tprev).count());
+        tprev = tnow;
+    }
+    if (dbg && (round <= 2 || env.all_rounds)) {   // per-chunk cost profile of the rounds' walked chunks
+        constexpr size_t DS = DBG_SLOTS;
+        std::vector<uint64_t> d(C * DS);
+        SCCG_HIP(hipMemcpyAsync(d.data(), A.dbg, C * DS * 8, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipStreamSynchronize(s));
+        std::vector<uint64_t> tk(C);
+        uint64_t sum[14] = {};
+        const int64_t rep = A.dbg_round > 0 ? A.dbg_round : round;   // (the round whose counters are kept)
+        for (size_t j = 0; j < C; j++) {
+            const bool mine = d[j * DS + 14] == (uint64_t)rep;
+            tk[j] = mine ? d[j * DS] : 0;
+            if (mine) for (int i = 0; i < 14; i++) sum[i] += d[j * DS + i];
+        }
+        std::vector<uint64_t> sorted = tk;
+        std::sort(sorted.begin(), sorted.end());
+        {
+            int dev = 0, khz = 0;
+            (void)hipGetDevice(&dev);
+            (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev);
+            fprintf(stderr, "[walk] wall clock rate %d kHz\n", khz);
+        }
+        fprintf(stderr, "[walk] r%lld chunk ticks(10ns): mean %.0f p50 %llu p90 %llu p99 %llu max %llu | totals: matches %llu "
+                "batches %llu wides %llu windows %llu cands %llu extbases %llu\n",
+                (long long)round, (double)sum[0] / C, (unsigned long long)sorted[C / 2], (unsigned long long)sorted[C * 9 / 10],
+                (unsigned long long)sorted[C * 99 / 100], (unsigned long long)sorted[C - 1],
+                (unsigned long long)sum[1], (unsigned long long)sum[2], (unsigned long long)sum[3],
+                (unsigned long long)sum[4], (unsigned long long)sum[5], (unsigned long long)sum[6]);
+        {   // launch spread: when the chunks' waves started and ended, from the first start
+            uint64_t s0 = ~0ull;
+            for (size_t j = 0; j < C; j++) if (d[j * DS + 14] == (uint64_t)rep && d[j * DS + 15] < s0) s0 = d[j * DS + 15];
+            std::vector<uint64_t> st, en;
+            for (size_t j = 0; j < C; j++)
+                if (d[j * DS + 14] == (uint64_t)rep) { st.push_back(d[j * DS + 15] - s0); en.push_back(d[j * DS + 15] - s0 + d[j * DS]); }
+            if (!st.empty()) {
+                std::sort(st.begin(), st.end());
+                std::sort(en.begin(), en.end());
+                const size_t m = st.size();
+                fprintf(stderr, "[walk] r%lld %zu waves: start p50 %llu p90 %llu max %llu | end p50 %llu p90 %llu p99 %llu max %llu (10ns)\n",
+                        (long long)round, m, (unsigned long long)st[m / 2], (unsigned long long)st[m * 9 / 10],
+                        (unsigned long long)st[m - 1], (unsigned long long)en[m / 2], (unsigned long long)en[m * 9 / 10],
+                        (unsigned long long)en[m * 99 / 100], (unsigned long long)en[m - 1]);
+            }
+        }
+        fprintf(stderr, "[walk] r1 step phases (10ns, summed over chunks): window %llu find %llu cand+lce %llu tail %llu "
+                "hash %llu wide %llu (wide positions %llu)\n",
+                (unsigned long long)sum[7], (unsigned long long)sum[8], (unsigned long long)sum[9], (unsigned long long)sum[10],
+                (unsigned long long)sum[11], (unsigned long long)sum[12], (unsigned long long)sum[13]);
+        std::vector<size_t> idx(C);
+        for (size_t j = 0; j < C; j++) idx[j] = j;
+        const size_t nshow = C < 5 ? C : 5;
+        std::partial_sort(idx.begin(), idx.begin() + nshow, idx.end(), [&](size_t a, size_t b) { return tk[a] > tk[b]; });
+        for (size_t q = 0; q < nshow; q++) {
+            const uint64_t* e = &d[idx[q] * DS];
+            fprintf(stderr, "   slow chunk %zu: ticks %llu matches %llu batches %llu wides %llu windows %llu cands %llu ext %llu "
+                    "| win %llu find %llu cand %llu tail %llu hash %llu wide %llu widepos %llu\n",
+                    idx[q], (unsigned long long)e[0], (unsigned long long)e[1], (unsigned long long)e[2],
+                    (unsigned long long)e[3], (unsigned long long)e[4], (unsigned long long)e[5], (unsigned long long)e[6],
+                    (unsigned long long)e[7], (unsigned long long)e[8], (unsigned long long)e[9], (unsigned long long)e[10],
+                    (unsigned long long)e[11], (unsigned long long)e[12], (unsigned long long)e[13]);
+        }
+    }
+    const int dbg_chunk = env.debug_chunk;
+    if (dbg && dbg_chunk >= 0 && dbg_chunk < A.C) {   // both trajectory buffers of one chunk
+        const size_t j = (size_t)dbg_chunk;
+        int32_t cur = 0, cn[2] = {0, 0}, ux = 0, up = 0, ex = 0, ep = 0, sq = 0;
+        SCCG_HIP(hipMemcpy(&cur, A.cur + j, 4, hipMemcpyDeviceToHost));
+        SCCG_HIP(hipMemcpy(&cn[0], A.cnt[0] + j, 4, hipMemcpyDeviceToHost));
+        SCCG_HIP(hipMemcpy(&cn[1], A.cnt[1] + j, 4, hipMemcpyDeviceToHost));
+        SCCG_HIP(hipMemcpy(&ux, A.usedX + j, 4, hipMemcpyDeviceToHost));
+        SCCG_HIP(hipMemcpy(&up, A.usedP + j, 4, hipMemcpyDeviceToHost));
+        SCCG_HIP(hipMemcpy(&ex, A.exitX + j, 4, hipMemcpyDeviceToHost));
+        SCCG_HIP(hipMemcpy(&ep, A.exitP + j, 4, hipMemcpyDeviceToHost));
+        SCCG_HIP(hipMemcpy(&sq, A.seedq + j, 4, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[chunk %zu] round %lld cur=%d used=(%d,%d) exit=(%d,%d) seedq=%d\n", j, (long long)round, cur, ux,
+                up, ex, ep, sq);
+        for (int b = 0; b < 2; b++) {
+            const int n = cn[b] < 80 ? cn[b] : 80;
+            std::vector<int32_t> tt(n > 0 ? n : 1), pp(tt.size()), ll(tt.size());
+            if (n > 0) {
+                SCCG_HIP(hipMemcpy(tt.data(), A.bt[b] + j * A.cap, n * 4, hipMemcpyDeviceToHost));
+                SCCG_HIP(hipMemcpy(pp.data(), A.bp[b] + j * A.cap, n * 4, hipMemcpyDeviceToHost));
+                SCCG_HIP(hipMemcpy(ll.data(), A.bl[b] + j * A.cap, n * 4, hipMemcpyDeviceToHost));
+            }
+            fprintf(stderr, "  buf%d (%d):", b, cn[b]);
+            for (int q = 0; q < n; q++) fprintf(stderr, " (%d,%d,%d)", tt[q], pp[q], ll[q]);
+            fprintf(stderr, "\n");
+        }
+    }
+    if (dbg && (round <= env.debug_rounds || round % 1000 == 0)) {
+        std::vector<int32_t> g(C), ex(C), ep(C), ux(C), up(C), cur(C), c0(C), c1(C);
+        SCCG_HIP(hipMemcpyAsync(g.data(), A.guess, C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipMemcpyAsync(ex.data(), A.exitX, C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipMemcpyAsync(ep.data(), A.exitP, C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipMemcpyAsync(ux.data(), A.usedX, C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipMemcpyAsync(up.data(), A.usedP, C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipMemcpyAsync(cur.data(), A.cur, C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipMemcpyAsync(c0.data(), A.cnt[0], C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipMemcpyAsync(c1.data(), A.cnt[1], C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipStreamSynchronize(s));
+        size_t ginv = 0, einv = 0, settled = 0;
+        for (size_t j = 0; j < C; j++) {
+            ginv += g[j] == INVALID;
+            einv += ex[j] == INVALID;
+            const int32_t px = j ? ex[j - 1] : startX, pp = j ? ep[j - 1] : startP;
+            settled += (px == ux[j] && pp == up[j]);
+        }
+        fprintf(stderr, "[walk] round %lld launched %d: guess INVALID %zu, exit INVALID %zu, settled %zu/%zu\n",
+                (long long)round, nlist, ginv, einv, settled, C);
+        std::vector<int32_t> stt(C);
+        SCCG_HIP(hipMemcpyAsync(stt.data(), A.status, C * 4, hipMemcpyDeviceToHost, s));
+        SCCG_HIP(hipStreamSynchronize(s));
+        int shown = 0;
+        for (size_t j = 1; j < C && shown < 6; j++) {
+            if (ex[j - 1] == ux[j] && ep[j - 1] == up[j]) continue;
+            shown++;
+            fprintf(stderr, "  unsettled %zu lo=%d guess=%d used=(%d,%d) pred_exit=(%d,%d) exit=(%d,%d) st=%d cur=%d cnt=%d/%d\n",
+                    j, (int)(j * A.S), g[j], ux[j], up[j], ex[j - 1], ep[j - 1], ex[j], ep[j], stt[j], cur[j], c0[j], c1[j]);
+            const int32_t b = cur[j];
+            const int32_t nshow = (b ? c1[j] : c0[j]) < 4 ? (b ? c1[j] : c0[j]) : 4;
+            std::vector<int32_t> tt(4), pp(4), ll(4);
+            SCCG_HIP(hipMemcpyAsync(tt.data(), A.bt[b] + j * A.cap, 16, hipMemcpyDeviceToHost, s));
+            SCCG_HIP(hipMemcpyAsync(pp.data(), A.bp[b] + j * A.cap, 16, hipMemcpyDeviceToHost, s));
+            SCCG_HIP(hipMemcpyAsync(ll.data(), A.bl[b] + j * A.cap, 16, hipMemcpyDeviceToHost, s));
+            SCCG_HIP(hipStreamSynchronize(s));
+            for (int q = 0; q < nshow; q++) fprintf(stderr, "      m%d (%d,%d,%d)\n", q, tt[q], pp[q], ll[q]);
+        }
+    }
+    return 0;
+}
+}  // namespace

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: full GPU test suite, then short benches (env variants in $VARIANTS, e.g.
-# "SCCG_STALE_BUDGET=2048 SCCG_WALK_CHUNK=8192"; "-" = defaults) and an optional SCCG_DEBUG trace.
+# "SCCG_WALK_CHUNK=8192"; "-" = defaults) and an optional SCCG_DEBUG trace.
 # Logs and bench lines go to $OUT/check (default prof_out/check).
 set -eo pipefail
 OUT=${OUT:-prof_out}/check
