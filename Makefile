@@ -2,6 +2,7 @@
 #   sccg-genome-compression_amd/lib/libsccg.so     C ABI (include/sccg.h) + HIP kernels
 #   sccg-genome-compression_amd/bin/compression    reference-compatible CLIs over the C ABI
 #   sccg-genome-compression_amd/bin/decompression
+#   sccg-genome-compression_amd/bin/fetch          regions of a record (sccg_reader_*)
 #   sccg-genome-compression_amd/tools/libsccg_synth.so, sccg_synth   synthetic pairs
 # and the test-only oracle (oracle/, plus oracle/_ref when /root/reference exists).
 PKG      := sccg-genome-compression_amd
@@ -32,7 +33,7 @@ $(LIB): $(OBJS)
 	@mkdir -p $(PKG)/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJS)
 
-cli: $(PKG)/bin/compression $(PKG)/bin/decompression
+cli: $(PKG)/bin/compression $(PKG)/bin/decompression $(PKG)/bin/fetch
 
 $(PKG)/bin/%: $(PKG)/cli/%.cpp $(LIB) include/sccg.h $(PKG)/cli/cli_common.h
 	@mkdir -p $(PKG)/bin

@@ -20,6 +20,10 @@
  *                                     (one chromosome split across GPUs)
  * sccg_reconstruct / _device          decompress_genome after 7z +       decompression.cpp:43-114,
  *                                     reconstruct_genome + file body     :117-279, :316-323
+ * sccg_reader_open / _device          reconstruct_genome's parse, kept    decompression.cpp:117-236
+ * sccg_reader_fetch / _device         ranges of its `result`             decompression.cpp:241-262
+ *   (sccg_reader_close, _length,        (no counterpart: the reference rebuilds the whole file)
+ *    _header)
  *
  * Conventions: status ints (0 = OK); the library never calls exit(); host buffers it returns are
  * malloc'ed and released with sccg_buf_free.  One context per GPU; a context is not re-entrant;
@@ -178,6 +182,52 @@ int sccg_reconstruct(sccg_ctx* ctx, const char* ref_fa, size_t ref_len, const ch
  * with out_cap too small it returns SCCG_E_NOMEM and sets *out_len to the size needed. */
 int sccg_reconstruct_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_len, const void* d_rec,
                             size_t rec_len, void* d_out, size_t out_cap, size_t* out_len, void* stream);
+
+/* Region reader: ranges of the target read from a record without rebuilding it.  The reference has
+ * no counterpart (it writes the whole of reconstructed_genome.fa); the sequence a reader addresses
+ * is `result` of decompression.cpp:241-274 after N insertion (:241-249) and lowercasing (:251-262),
+ * i.e. the body of reconstructed_genome.fa with its '\n' removed.  Position j of a region is byte j
+ * of that string; regions are 0-based and half-open.
+ *
+ * sccg_reader_open does reconstruct_genome's one-time work once (reference strip :105-110, run
+ * lines :126-207, the record line's tokens :210-236 as a block index) and returns exactly the
+ * status sccg_reconstruct returns for the same inputs: SCCG_E_FORMAT, _PARSE, _RANGE (every token
+ * is checked, :223-229) and the N-beyond-sequence check; on any error *out is NULL.  After an open
+ * that succeeds a fetch decodes only valid tokens and re-checks nothing.  The _device form takes
+ * device pointers and a hipStream_t (NULL = the context's own stream).
+ *
+ * A reader owns what it keeps, in device allocations of its own (the context's buffers are reused by
+ * its next call): R', the record line, three int64 per 64 record-line bytes, both run lists and the
+ * header bytes -- about |R'| + |record line| * 11 / 8 + 16 * N runs + 8 * lowercase runs + 12 KiB.
+ * Inputs are not referenced after open returns.  Several readers may be open on one context;
+ * sccg_compress / sccg_reconstruct on that context do not disturb them.  A reader uses its context's
+ * streams and shares its non-reentrancy (one call at a time per context, readers included); close
+ * every reader before sccg_ctx_destroy. */
+typedef struct sccg_reader sccg_reader;
+typedef struct { int64_t begin, end; } sccg_region;   /* 0-based, half-open, in sequence positions */
+
+int sccg_reader_open(sccg_ctx* ctx, const char* ref_fa, size_t ref_len, const char* rec_text, size_t rec_len,
+                     sccg_reader** out);
+int sccg_reader_open_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_len, const void* d_rec, size_t rec_len,
+                            sccg_reader** out, void* stream);
+void sccg_reader_close(sccg_reader* reader);                         /* NULL: no-op */
+int64_t sccg_reader_length(const sccg_reader* reader);               /* bases in the sequence; -1 for NULL */
+const char* sccg_reader_header(const sccg_reader* reader, size_t* len); /* the record's header line ('>'
+                                                                        included) without '\n'; len 0 if none */
+
+/* The regions' bases, concatenated in the order given, no separators, no wrapping: region i starts
+ * at byte sum_{k<i}(end_k - begin_k).  Regions may overlap, repeat, be empty and come in any order;
+ * n == 0 gives an empty output.  One kernel launch and one copy of the region list per call whatever
+ * n is; the work follows the bases asked for.  SCCG_E_INVALID for a NULL reader / output, NULL
+ * regions with n > 0, or a region outside 0 <= begin <= end <= length (sccg_last_error names the
+ * first one; nothing is written).  sccg_reader_fetch returns a malloc'ed buffer (sccg_buf_free).
+ * The _device form writes to d_out (capacity out_cap) and sets *out_len; d_out == NULL is a size
+ * query, out_cap too small returns SCCG_E_NOMEM with *out_len = the size needed.  Both synchronise
+ * before returning. */
+#define SCCG_FETCH_UPPER 1u   /* ignore the lowercase runs (decompression.cpp:251-262 skipped) */
+int sccg_reader_fetch(sccg_reader* reader, const sccg_region* regions, size_t n, uint32_t flags, sccg_buf* out);
+int sccg_reader_fetch_device(sccg_reader* reader, const sccg_region* regions /*host*/, size_t n, uint32_t flags,
+                             void* d_out, size_t out_cap, size_t* out_len, void* stream);
 
 void sccg_buf_free(sccg_buf* b);
 

@@ -1,0 +1,91 @@
+// fetch -- `fetch <record_file> <reference_file> <region>...`: regions of the target read from an
+// extracted compressed_genome.txt (no 7z call) without rebuilding it (sccg_reader_*).  A region is
+// `begin-end`, 1-based and inclusive as in `samtools faidx`, or a bare `pos` (one base).  Per region
+// it prints `>name:begin-end` (name: the record's header line without its '>', `seq` when it has
+// none) and the bases wrapped at 50 columns (decompression.cpp:266-274's width).  All regions go in
+// one sccg_reader_fetch call.  Exit code 1 on usage / region / open / format errors; the regions
+// are parsed before the GPU is touched.
+#include "cli_common.h"
+
+// decimal digits only, no sign, fits int64
+static bool parse_pos(const std::string& s, int64_t* v) {
+    if (s.empty() || s.size() > 18) return false;
+    int64_t x = 0;
+    for (char c : s) {
+        if (c < '0' || c > '9') return false;
+        x = x * 10 + (c - '0');
+    }
+    *v = x;
+    return true;
+}
+
+int main(int argc, char* argv[]) {
+    if (argc < 4) {
+        std::cerr << "Usage: " << argv[0] << " <record_file> <reference_file> <region>...\n"
+                  << "  region: begin-end (1-based, inclusive) or pos\n";
+        return 1;
+    }
+    const std::string rec_path = argv[1], ref_path = argv[2];
+    std::vector<sccg_region> regions;
+    for (int i = 3; i < argc; i++) {
+        const std::string a = argv[i];
+        const size_t dash = a.find('-');
+        int64_t b = 0, e = 0;
+        const bool ok = dash == std::string::npos ? parse_pos(a, &b) && (e = b, true)
+                                                  : parse_pos(a.substr(0, dash), &b) && parse_pos(a.substr(dash + 1), &e);
+        if (!ok || b < 1 || e < b) {
+            std::cerr << "Error: malformed region '" << a << "' (begin-end, 1-based, inclusive, begin <= end)\n";
+            return 1;
+        }
+        regions.push_back(sccg_region{b - 1, e});
+    }
+    std::string ref, rec;
+    if (!slurp(ref_path, ref)) {
+        std::cerr << "Greska pri otvaranju reference: " << ref_path << "\n";
+        return 1;
+    }
+    if (!slurp(rec_path, rec)) {
+        std::cerr << "Greska pri otvaranju datoteke: " << rec_path << "\n";
+        return 1;
+    }
+    sccg_ctx* ctx = nullptr;
+    int rc = sccg_ctx_create(cli_device(), &ctx);
+    if (rc) {
+        std::cerr << "Error: no usable GPU (sccg_ctx_create rc=" << rc << ")\n";
+        return 1;
+    }
+    sccg_reader* rd = nullptr;
+    rc = sccg_reader_open(ctx, ref.data(), ref.size(), rec.data(), rec.size(), &rd);
+    if (rc) {
+        std::cerr << "Error opening the record: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    sccg_buf seq{};
+    rc = sccg_reader_fetch(rd, regions.data(), regions.size(), 0, &seq);
+    if (rc) {
+        std::cerr << "Error fetching: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_reader_close(rd);
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    size_t hlen = 0;
+    const char* hdr = sccg_reader_header(rd, &hlen);
+    const std::string name = hlen > 1 ? std::string(hdr + 1, hlen - 1) : std::string("seq");
+    std::string out;
+    size_t at = 0;
+    for (const sccg_region& r : regions) {
+        out += ">" + name + ":" + std::to_string(r.begin + 1) + "-" + std::to_string(r.end) + "\n";
+        const size_t len = (size_t)(r.end - r.begin);
+        for (size_t k = 0; k < len; k += 50) {
+            out.append(seq.data + at + k, len - k < 50 ? len - k : 50);
+            out += '\n';
+        }
+        at += len;
+    }
+    std::cout << out;
+    sccg_buf_free(&seq);
+    sccg_reader_close(rd);
+    sccg_ctx_destroy(ctx);
+    return 0;
+}

@@ -57,3 +57,21 @@ int dc_format_index(int64_t nres, const DcRuns& nr, const DcRuns& lr, int64_t* d
 // first waits for wait_before (the index's stream).
 int dc_format(const uint8_t* d_dec, int64_t nres, const DcRuns& nr, const DcRuns& lr, const int64_t* d_index, uint8_t* d_out,
               hipStream_t s, hipEvent_t wait_before);
+
+// What a region fetch reads (a reader's own copies, sccg_api.cpp): the record line and its 64-byte
+// block index (state, decoded offset, running p: dc_decode_prepare's d_lp, d_off, d_dsum), R' and
+// both run lists (cum: the N runs' only).  Byte buffers carry the usual readable slack.
+struct DcFetchSrc {
+    const uint8_t* rec;
+    int64_t nrec;
+    const int64_t* bin;
+    const int64_t* boff;
+    const int64_t* bdsum;
+    const uint8_t* R;
+    DcRuns nr, lr;
+};
+// d_out[0, F) = the sequence bytes of regions [d_beg[i], d_beg[i] + d_pre[i + 1] - d_pre[i]), i < nreg,
+// concatenated (d_pre: exclusive prefix of the lengths, d_pre[nreg] = F); upper: no lowercase runs.
+// One launch whatever nreg is; regions and tokens were validated by the caller.
+int dc_fetch(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, bool upper,
+             uint8_t* d_out, hipStream_t s);

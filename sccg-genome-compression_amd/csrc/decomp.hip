@@ -922,6 +922,184 @@ __global__ __launch_bounds__(256) void k_format_out(const uint8_t* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Region fetch (sccg_reader_fetch): bytes [begin, end) of the sequence -- result of
+// decompression.cpp:241-262, N inserted and lowercased, no '\n' -- for a batch of regions,
+// concatenated in the order given, from the state a reader keeps (DcFetchSrc).  One launch for the
+// whole batch.  The flat output is tiled as in the formatter: a block owns OB bytes of it, 16-byte
+// aligned in memory, a wave FT_W = 1 KiB of those, a lane 16.  A wave finds its first region in the
+// prefix of region lengths and then takes the spans [j0, j1) of sequence positions its bytes cover
+// one after the other.  Per span: positions -> decoded offsets [d0, d1) over the N runs, decoded
+// offsets -> record blocks [b0, b1] over boff, the k_tok_fill2 parse of just those blocks with
+// every literal and token copy clipped to [d0, d1) into the wave's LDS tile (a long token is entered
+// at R' + p + (d0 - o)), then the formatter's per-byte N / lowercase walk over the tile.  Every
+// search is a wave-wide 64-ary one (64 probes per step); nothing is swept end to end, no scratch
+// beyond LDS.  The reader's open has checked every token and run: nothing is re-checked here.
+// ---------------------------------------------------------------------------------------------
+constexpr int FT_W = 64 * OPT;
+static_assert(FT_W * WPB == OB, "a block of WPB waves owns OB output bytes");
+
+// first m in [a, b) with pred(m), b if none; pred monotone (false .. true), a and b wave-uniform
+template <typename P>
+__device__ __forceinline__ int64_t wave_first(int64_t a, int64_t b, P&& pred) {
+    const int lane = lane_id();
+    while (b - a > 64) {
+        const int64_t step = (b - a + 63) >> 6;
+        const int64_t m = a + (int64_t)lane * step + step - 1;   // the last entry of this lane's chunk
+        const unsigned long long t = __ballot(m >= b || pred(m));
+        if (!t) return b;   // (the last chunk ends exactly at b - 1 and is false there)
+        const int c = __ffsll((long long)t) - 1;
+        const int64_t mc = a + (int64_t)c * step + step - 1;
+        a += (int64_t)c * step;
+        b = mc < b ? mc : b;   // pred(mc) holds (or mc is past the end): the answer is in [a, mc]
+    }
+    const unsigned long long t = __ballot(a + lane < b && pred(a + lane));
+    return t ? a + (__ffsll((long long)t) - 1) : b;
+}
+
+struct FetchArgs {
+    DcFetchSrc S;
+    const int64_t* pre;   // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
+    const int64_t* beg;   // nreg: region begins
+    int64_t nreg, F, o_first, nlr;   // nlr: lowercase runs looked at (0 with SCCG_FETCH_UPPER)
+    uint8_t* out;
+};
+
+__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch(const FetchArgs A) {
+    __shared__ uint8_t tile[WPB][FT_W];
+    __shared__ uint8_t stg[WPB][2 * TK_B];
+    const int lane = lane_id();
+    uint8_t* sdec = tile[wave_in_block()];
+    uint8_t* st = stg[wave_in_block()];
+    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
+    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
+    int64_t f = base < 0 ? 0 : base;
+    if (f >= fend) return;
+    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 output bytes
+    const uint8_t* __restrict__ rec = A.S.rec;
+    const int64_t n = A.S.nrec, nblk = (n + TK_B - 1) / TK_B;
+    const int64_t* __restrict__ boff = A.S.boff;
+    const int32_t* __restrict__ ns = A.S.nr.start;
+    const int32_t* __restrict__ nl = A.S.nr.len;
+    const int64_t* __restrict__ ncum = A.S.nr.cum;
+    const int32_t* __restrict__ ls = A.S.lr.start;
+    const int32_t* __restrict__ ll = A.S.lr.len;
+    const int64_t nn = A.S.nr.n, nlr = A.nlr;
+    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
+    const int64_t* __restrict__ pre = A.pre;
+    // the region holding flat byte f: the last i with pre[i] <= f (an empty region never is)
+    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+    while (f < fend) {
+        if (pre[i + 1] <= f) {   // the next region that is not empty: usually i + 1, else searched for
+            i++;
+            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+        }
+        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
+        const int64_t j0 = A.beg[i] + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
+        // positions -> decoded offsets: the N positions before j0 and before j1
+        const int64_t rn0 = wave_first(0, nn, [&](int64_t m) { return (int64_t)ns[m] + nl[m] > j0; });
+        const int64_t rn1 = wave_first(rn0, nn, [&](int64_t m) { return (int64_t)ns[m] + nl[m] > j1; });
+        const int64_t d0 = j0 - n_before_at(ns, nl, ncum, nn, rn0, j0), d1 = j1 - n_before_at(ns, nl, ncum, nn, rn1, j1);
+        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
+        if (d1 > d0) {
+            // record blocks holding decoded bytes d0 and d1 - 1 (a block's bytes: [boff[b], boff[b + 1]))
+            const int64_t b0 = wave_first(1, nblk, [&](int64_t m) { return boff[m] > d0; }) - 1;
+            const int64_t b1 = wave_first(b0 + 1, nblk, [&](int64_t m) { return boff[m] >= d1; }) - 1;
+            for (int64_t b = b0; b <= b1; b++) {
+                // k_tok_fill2's parse of block b
+                const int64_t rb = b * TK_B, ri = rb + lane;
+                const uint8_t c = ri < n ? rec[ri] : (uint8_t)',';
+                wave_sync();   // (the staged bytes of the block before are no longer read)
+                st[lane] = c;
+                st[TK_B + lane] = ri + TK_B < n ? rec[ri + TK_B] : (uint8_t)0;
+                wave_sync();
+                const RlView v{st - RL_BEHIND, rb, n, TK_B};   // v.at(q) = st[q - rb]
+                const bool par = ri < n && (c == '(' || c == ')');
+                const unsigned long long pm = __ballot(par) & ((1ull << lane) - 1ull);
+                const bool inside = pm ? st[63 - __clzll((long long)pm)] == '(' : A.S.bin[b] != 0;
+                int64_t contrib = 0, d = 0;
+                bool tok = false;
+                if (ri < n) {
+                    if (c == '(') {
+                        int64_t comma = -1, close = -1, l = 0;
+                        for (int64_t q = ri + 1; q < n && q < ri + 32; q++) {
+                            const uint8_t cq = v.at(q);
+                            if (cq == ',' && comma < 0) comma = q;
+                            if (cq == ')') { close = q; break; }
+                            if (cq == '(') break;
+                        }
+                        if (comma > 0 && close > comma && parse_int_v(v, ri + 1, comma, &d) &&
+                            parse_int_v(v, comma + 1, close, &l) && l >= 0) {
+                            tok = true;
+                            contrib = l;
+                        }
+                    } else if (c == ')') {
+                        contrib = inside ? 0 : 1;
+                    } else if (!inside) {
+                        contrib = 1;
+                    }
+                }
+                const int64_t o = boff[b] + wave_incl_add(contrib) - contrib;
+                const int64_t p = A.S.bdsum[b] + wave_incl_add(d);   // running p, this token included
+                if (!tok && contrib == 1 && c != '(' && o >= d0 && o < d1) sdec[o - d0] = c;
+                unsigned long long tm = __ballot(tok && o < d1 && o + contrib > d0);
+                while (tm) {
+                    const int j = __ffsll((long long)tm) - 1;   // (wave-uniform: the token's fields by readlane)
+                    tm &= tm - 1;
+                    const int64_t pj = readlane64(p, j), oj = readlane64(o, j), lj = readlane64(contrib, j);
+                    const int64_t a = oj > d0 ? oj : d0, e = oj + lj < d1 ? oj + lj : d1;
+                    const uint8_t* __restrict__ src = A.S.R + pj + (a - oj);   // not walked there from the token's start
+                    uint8_t* dst = sdec + (a - d0);
+                    const int cnt = (int)(e - a), k = lane * OPT;   // cnt <= FT_W: one 16-byte load per lane
+                    if (k < cnt) {
+                        const uint4 x = load16u(src + k);   // (up to 15 bytes past the token: R' carries the slack)
+                        const uint32_t w4[4] = {x.x, x.y, x.z, x.w};
+                        const int m = cnt - k < OPT ? cnt - k : OPT;
+#pragma unroll
+                        for (int q = 0; q < OPT; q++)
+                            if (q < m) dst[k + q] = (uint8_t)(w4[q >> 2] >> (8 * (q & 3)));
+                    }
+                }
+            }
+            wave_sync();
+        }
+        // the lane's bytes of this span: the formatter's per-byte walk over the runs, without the wrap
+        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
+        if (ga < gb) {
+            int64_t j = j0 + (ga - f), rn = rn0, rl = rl0;
+            int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot, l_s = INT64_MAX, l_e = INT64_MAX;
+            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+            if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
+            uint64_t lo = 0, hi = 0;
+            const int k0 = (int)(ga - g0), k1 = (int)(gb - g0);
+            for (int k = k0; k < k1; k++) {
+                while (j >= n_e) {
+                    rn++;
+                    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+                    else { n_s = n_e = INT64_MAX; n_b = ntot; }
+                }
+                while (j >= l_e) {
+                    rl++;
+                    if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
+                    else l_s = l_e = INT64_MAX;
+                }
+                uint32_t c = j >= n_s ? (uint32_t)'N' : (uint32_t)sdec[j - n_b - d0];
+                if (j >= l_s) c = c_tolower((uint8_t)c);
+                j++;
+                if (k < 8) lo |= (uint64_t)c << (8 * k);
+                else hi |= (uint64_t)c << (8 * (k - 8));
+            }
+            if (k0 == 0 && k1 == OPT) {
+                store16(A.out + g0, lo, hi);
+            } else {
+                for (int k = k0; k < k1; k++) A.out[g0 + k] = (uint8_t)((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8))) & 0xff);
+            }
+        }
+        wave_sync();   // (the tile is read before the next span fills it)
+        f = fe;
+    }
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1108,6 +1286,16 @@ int dc_format(const uint8_t* d_dec, int64_t nres, const DcRuns& nr, const DcRuns
     PROF_LAUNCH(PROF_DC_FORMAT, s, k_format_out, dim3((unsigned)g.nblk), dim3(256), 0, s, d_dec, nres, g.total, g.o_first,
                 (const int32_t*)nr.start, (const int32_t*)nr.len, (const int64_t*)nr.cum, nr.n,
                 (const int32_t*)lr.start, (const int32_t*)lr.len, lr.n, d_index, d_out);
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
+int dc_fetch(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, bool upper,
+             uint8_t* d_out, hipStream_t s) {
+    if (F <= 0) return 0;
+    FetchArgs A{src, d_pre, d_beg, nreg, F, -(int64_t)((uintptr_t)d_out & 15), upper ? 0 : src.lr.n, d_out};
+    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
+    PROF_LAUNCH(PROF_FETCH, s, k_fetch, dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
     SCCG_HIP(hipGetLastError());
     return 0;
 }

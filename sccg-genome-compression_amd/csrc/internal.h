@@ -22,6 +22,7 @@ enum ProfId {
     PROF_DC_DECODE,      // k_tok_fill
     PROF_DC_FORMAT,      // k_format
     PROF_WALK_CARRY,     // k_walk<., true>: a round's carry launch
+    PROF_FETCH,          // k_fetch (sccg_reader_fetch)
     PROF_COUNT
 };
 void prof_begin(hipStream_t s, int id);

@@ -215,6 +215,21 @@ struct sccg_ctx {
     }
 };
 
+// A region reader (sccg_reader_open): what a fetch reads, in device memory of its own -- never a
+// pooled slot of the context, which the next compress / reconstruct reuses.
+struct sccg_reader {
+    sccg_ctx* ctx = nullptr;
+    void* mem = nullptr;        // R', the record line, its block index, both run lists (src points into it)
+    DcFetchSrc src{};
+    int64_t length = 0;         // bases in the sequence (reconstruct_impl's nres)
+    std::string header;         // the header line, '>' included, no '\n'; empty: none
+    void* d_reg = nullptr;      // a fetch's region list: device copy and its pinned host image
+    int64_t* h_reg = nullptr;
+    size_t reg_cap = 0;
+    void* d_out = nullptr;      // sccg_reader_fetch's device output
+    size_t out_cap = 0;
+};
+
 #define TRY(expr)                                  \
     do {                                           \
         int rc_ = (expr);                          \
@@ -1086,25 +1101,17 @@ int compress_files_impl(sccg_ctx* ctx, const sccg_params& P, const char* ref_pat
 // -------------------------------------------------------------------------------------------
 // reconstruction (decompression.cpp)
 // -------------------------------------------------------------------------------------------
-int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_t* rec, int64_t n, uint8_t* out,
-                     int64_t out_cap, int64_t* out_len, bool size_only) {
-    hipStream_t s = ctx->stream;
-    GET(int64_t, sc, B_SCAL, 64);
-    // ---- reference (decompression.cpp:47-58, 105-110), first, on the side stream beside everything
-    //      that follows: its filter depends on the N line only when that line is exactly "," (then it
-    //      keeps the N's, FILTER_UPPER), so the usual filter starts now and that rare case redoes it
-    //      once the lines are known.  (Its length |R'| stays on the device, sc[9], until the range
-    //      check and the parse's readback.)
-    GET(uint8_t, Rp, B_RP, rn + 64);   // (only R' is read: the strip writes no R here)
-    HIPTRY(hipEventRecord(ctx->ev_fork, s));
-    HIPTRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-    TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, nullptr, sc + 8, nullptr, nullptr, FILTER_DROP_UPPERN_ONLY, Rp, 1, ctx->side));
-    HIPTRY(hipEventRecord(ctx->ev_rstrip, ctx->side));
-    struct JoinSide {   // every exit path: the main stream waits for the strip (a later call reuses Rp)
-        sccg_ctx* c;
-        hipStream_t st;
-        ~JoinSide() { (void)hipStreamWaitEvent(st, c->ev_rstrip, 0); }
-    } join_side{ctx, s};
+// The record file's lines (decompression.cpp:66-101): header (optional), lowercase runs, N runs,
+// record line, as device pointers into rec; the error word (sc + 40) is zeroed on the way.
+struct RecLines {
+    int64_t hlen = 0;   // the header line's length, 0: none
+    const uint8_t* lower = nullptr;
+    const uint8_t* nline = nullptr;
+    const uint8_t* enc = nullptr;
+    int64_t nlower = 0, nnl = 0, nenc = 0;
+    bool n_is_comma = false;   // the N line is exactly ",": the reference keeps its N's
+};
+int record_lines(sccg_ctx* ctx, const uint8_t* rec, int64_t n, int64_t* sc, hipStream_t s, RecLines* L) {
     // the line ends: one pass collects every '\n' (a record file holds 2-3); more than DC_NL_CAP
     // of them -> four ordered first-match searches.  (Queued ahead of the strip, the search itself
     // finished earlier, but its one-wave readback then waited ~40 us for a slot behind the strip's
@@ -1138,21 +1145,51 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     const bool has_hdr = end[0] > 0 && first == '>';
     const int li = has_hdr ? 1 : 0;
     for (int i = 1; i <= li + 2; i++)
-        if (start[i] >= n + (i == 0)) return ctx->fail(SCCG_E_FORMAT, "record file misses line %d", i + 1);
-    const uint8_t* lower = rec + start[li];
-    const int64_t nlower = end[li] - start[li];
-    const uint8_t* nline = rec + start[li + 1];
-    const int64_t nnl = end[li + 1] - start[li + 1];
-    const uint8_t* enc = rec + start[li + 2];
-    const int64_t nenc = end[li + 2] - start[li + 2];
-
-    bool n_is_comma = false;
-    if (nnl == 1) {
+        if (start[i] >= n) return ctx->fail(SCCG_E_FORMAT, "record file misses line %d", i + 1);
+    L->hlen = has_hdr ? end[0] : 0;
+    L->lower = rec + start[li];
+    L->nlower = end[li] - start[li];
+    L->nline = rec + start[li + 1];
+    L->nnl = end[li + 1] - start[li + 1];
+    L->enc = rec + start[li + 2];
+    L->nenc = end[li + 2] - start[li + 2];
+    if (L->nnl == 1) {
         uint8_t c = 0;
-        const RbItem it{nline, &c, 1};
+        const RbItem it{L->nline, &c, 1};
         TRY(dev_readback(&it, 1, s));
-        n_is_comma = c == ',';
+        L->n_is_comma = c == ',';
     }
+    return SCCG_OK;
+}
+
+int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_t* rec, int64_t n, uint8_t* out,
+                     int64_t out_cap, int64_t* out_len, bool size_only) {
+    hipStream_t s = ctx->stream;
+    GET(int64_t, sc, B_SCAL, 64);
+    // ---- reference (decompression.cpp:47-58, 105-110), first, on the side stream beside everything
+    //      that follows: its filter depends on the N line only when that line is exactly "," (then it
+    //      keeps the N's, FILTER_UPPER), so the usual filter starts now and that rare case redoes it
+    //      once the lines are known.  (Its length |R'| stays on the device, sc[9], until the range
+    //      check and the parse's readback.)
+    GET(uint8_t, Rp, B_RP, rn + 64);   // (only R' is read: the strip writes no R here)
+    HIPTRY(hipEventRecord(ctx->ev_fork, s));
+    HIPTRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+    TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, nullptr, sc + 8, nullptr, nullptr, FILTER_DROP_UPPERN_ONLY, Rp, 1, ctx->side));
+    HIPTRY(hipEventRecord(ctx->ev_rstrip, ctx->side));
+    struct JoinSide {   // every exit path: the main stream waits for the strip (a later call reuses Rp)
+        sccg_ctx* c;
+        hipStream_t st;
+        ~JoinSide() { (void)hipStreamWaitEvent(st, c->ev_rstrip, 0); }
+    } join_side{ctx, s};
+    RecLines L;
+    {
+        const int rc = record_lines(ctx, rec, n, sc, s, &L);
+        if (rc) return rc;
+    }
+    int32_t* d_err = reinterpret_cast<int32_t*>(sc + 40);
+    const uint8_t *lower = L.lower, *nline = L.nline, *enc = L.enc;
+    const int64_t nlower = L.nlower, nnl = L.nnl, nenc = L.nenc;
+    const bool n_is_comma = L.n_is_comma;
     if (n_is_comma) {   // the N line is ",": the reference keeps its N's (redo the strip behind the first)
         HIPTRY(hipEventRecord(ctx->ev_fork, s));
         HIPTRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
@@ -1247,7 +1284,7 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     if (err & 1) return ctx->fail(SCCG_E_PARSE, "record text outside the run/token grammar");
     if (err & 2) return ctx->fail(SCCG_E_RANGE, "token exceeds the reference (decompression.cpp:223-229)");
     const int64_t nres = D + nr.total;
-    const int64_t hlen = has_hdr ? end[0] : 0;
+    const int64_t hlen = L.hlen;
     const int64_t total = hlen + 1 + nres + (nres > 0 ? (nres - 1) / 50 : 0) + 1;
     if (size_only || (err & 4) || total > out_cap) {
         // the record line checks the token range in its fill: a size query or an early error
@@ -1285,6 +1322,197 @@ int reconstruct_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     }
     ctx->stats.target_bases = nres;
     ctx->stats.reference_bases = nRp;
+    return SCCG_OK;
+}
+
+
+// -------------------------------------------------------------------------------------------
+// region reader (sccg_reader_*): reconstruct_impl's one-time work, kept
+// -------------------------------------------------------------------------------------------
+int reader_alloc_fail(sccg_ctx* ctx, hipError_t e, size_t bytes) {
+    (void)hipGetLastError();
+    return ctx->fail(e == hipErrorOutOfMemory ? SCCG_E_NOMEM : SCCG_E_HIP, "reader allocation of %zu bytes failed", bytes);
+}
+
+// The front half of reconstruct_impl on the one stream -- lines, reference strip, run lines, the
+// record line's block index, every check (same statuses, same order as the size query) -- then
+// copies of what a fetch reads into one allocation of the reader's own: the context's slots are
+// reused by the next call.
+int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_t* rec, int64_t n, sccg_reader* rd) {
+    hipStream_t s = ctx->stream;
+    GET(int64_t, sc, B_SCAL, 64);
+    RecLines L;
+    {
+        const int rc = record_lines(ctx, rec, n, sc, s, &L);
+        if (rc) return rc;
+    }
+    int32_t* d_err = reinterpret_cast<int32_t*>(sc + 40);
+    const uint8_t *lower = L.lower, *nline = L.nline, *enc = L.enc;
+    const int64_t nlower = L.nlower, nnl = L.nnl, nenc = L.nenc;
+    const bool n_is_comma = L.n_is_comma;
+    // reference (decompression.cpp:47-58, 105-110): the N line "," keeps its N's (FILTER_UPPER)
+    GET(uint8_t, Rp, B_RP, rn + 64);
+    TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, nullptr, sc + 8, nullptr, nullptr,
+              n_is_comma ? FILTER_UPPER : FILTER_DROP_UPPERN_ONLY, Rp, 1, s));
+    GET(int64_t, lp2, B_D_LP2, nenc + 1);
+    GET(int64_t, dlt2, B_D_DLT2, nenc + 1);
+    GET(int64_t, part2, B_PARTIAL2, scan_partials_needed(nenc + 1) + 16);
+    GET(int64_t, contrib, B_D_CONTRIB, nenc + 1);
+    GET(int64_t, doff, B_D_OFF, nenc + 1);
+    GET(int64_t, dsum, B_D_DSUM, nenc + 1);
+    const int64_t nmax = nlower > nnl ? nlower : nnl;
+    GET(int64_t, lp, B_D_LP, nmax + 4);
+    GET(int64_t, flag, B_D_FLAG, nmax + 4 + 264);
+    GET(int64_t, dlt, B_D_DLT, nmax + 4 + 264);
+    GET(int64_t, part, B_PARTIAL, scan_partials_needed(nmax + 4) + 16);
+    GET(int32_t, ls, B_D_LS, dc_run_cap(nlower));
+    GET(int32_t, ll, B_D_LL, dc_run_cap(nlower));
+    GET(int64_t, lc, B_D_LC, dc_run_cap(nlower));
+    GET(int32_t, ns, B_D_NS, dc_run_cap(nnl));
+    GET(int32_t, nlr, B_D_NL, dc_run_cap(nnl));
+    GET(int64_t, nc, B_D_NC, dc_run_cap(nnl));
+    DcRuns lr{}, nr{};
+    lr.start = ls; lr.len = ll; lr.cum = lc;
+    nr.start = ns; nr.len = nlr; nr.cum = nc;
+    TRY(dc_parse_runs2(lower, nlower, &lr, sc + 14, nline, nnl, &nr, sc + 16, lp, flag, dlt, part, d_err, s));
+    TRY(dc_decode_prepare(enc, nenc, lp2, contrib, dlt2, doff, dsum, part2, d_err, sc + 12, s));
+    TRY(dc_n_check(nr, sc + 16, sc + 12, d_err, s));
+    int64_t D = 0, nRp = 0, cnt[4] = {0, 0, 0, 0};
+    int32_t err = 0;
+    {
+        const RbItem it[4] = {{sc + 12, &D, (int)sizeof D}, {d_err, &err, (int)sizeof err}, {sc + 14, cnt, (int)sizeof cnt},
+                              {sc + 9, &nRp, (int)sizeof nRp}};
+        TRY(dev_readback(it, 4, s));
+    }
+    if (err & 1) return ctx->fail(SCCG_E_PARSE, "record text outside the run/token grammar");
+    // the full token range check (decompression.cpp:223-229): what lets a fetch re-check nothing
+    TRY(dc_tok_range(enc, nenc, lp2, doff, dsum, sc + 9, d_err, s));
+    {
+        const RbItem it{d_err, &err, (int)sizeof err};
+        TRY(dev_readback(&it, 1, s));
+    }
+    if (err & 2) return ctx->fail(SCCG_E_RANGE, "token exceeds the reference (decompression.cpp:223-229)");
+    if (err & 4) return ctx->fail(SCCG_E_PARSE, "N positions beyond the sequence");
+    lr.n = cnt[0]; lr.total = cnt[1];
+    nr.n = cnt[2]; nr.total = cnt[3];
+
+    // ---- the reader's own memory: one allocation, 256-byte aligned parts, DPAD behind byte buffers
+    const int64_t nblk = (nenc + 63) / 64;
+    size_t off = 0;
+    auto part_at = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_R = part_at((size_t)nRp + DPAD), o_rec = part_at((size_t)nenc + DPAD);
+    const size_t o_bin = part_at((size_t)nblk * 8), o_boff = part_at((size_t)nblk * 8), o_bdsum = part_at((size_t)nblk * 8);
+    const size_t o_ns = part_at((size_t)nr.n * 4), o_nl = part_at((size_t)nr.n * 4), o_nc = part_at((size_t)nr.n * 8);
+    const size_t o_ls = part_at((size_t)lr.n * 4), o_ll = part_at((size_t)lr.n * 4);
+    const size_t bytes = off + 256;
+    const hipError_t e = hipMalloc(&rd->mem, bytes);
+    if (e != hipSuccess) { rd->mem = nullptr; return reader_alloc_fail(ctx, e, bytes); }
+    uint8_t* m = reinterpret_cast<uint8_t*>(rd->mem);
+    auto keep = [&](size_t at, const void* src, size_t nbytes) {
+        return nbytes ? hipMemcpyAsync(m + at, src, nbytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    };
+    HIPTRY(keep(o_R, Rp, (size_t)nRp));
+    HIPTRY(keep(o_rec, enc, (size_t)nenc));
+    HIPTRY(keep(o_bin, lp2, (size_t)nblk * 8));
+    HIPTRY(keep(o_boff, doff, (size_t)nblk * 8));
+    HIPTRY(keep(o_bdsum, dsum, (size_t)nblk * 8));
+    HIPTRY(keep(o_ns, ns, (size_t)nr.n * 4));
+    HIPTRY(keep(o_nl, nlr, (size_t)nr.n * 4));
+    HIPTRY(keep(o_nc, nc, (size_t)nr.n * 8));
+    HIPTRY(keep(o_ls, ls, (size_t)lr.n * 4));
+    HIPTRY(keep(o_ll, ll, (size_t)lr.n * 4));
+    if (L.hlen) {
+        rd->header.resize((size_t)L.hlen);
+        HIPTRY(hipMemcpyAsync(&rd->header[0], rec, (size_t)L.hlen, hipMemcpyDeviceToHost, s));
+    }
+    HIPTRY(hipStreamSynchronize(s));
+    DcFetchSrc& S = rd->src;
+    S.rec = m + o_rec;
+    S.nrec = nenc;
+    S.bin = reinterpret_cast<const int64_t*>(m + o_bin);
+    S.boff = reinterpret_cast<const int64_t*>(m + o_boff);
+    S.bdsum = reinterpret_cast<const int64_t*>(m + o_bdsum);
+    S.R = m + o_R;
+    S.nr = DcRuns{reinterpret_cast<int32_t*>(m + o_ns), reinterpret_cast<int32_t*>(m + o_nl),
+                  reinterpret_cast<int64_t*>(m + o_nc), nr.n, nr.total};
+    S.lr = DcRuns{reinterpret_cast<int32_t*>(m + o_ls), reinterpret_cast<int32_t*>(m + o_ll), nullptr, lr.n, lr.total};
+    rd->length = D + nr.total;
+    return SCCG_OK;
+}
+
+void reader_free(sccg_reader* rd) {
+    if (!rd) return;
+    (void)hipSetDevice(rd->ctx->device);
+    if (rd->mem) (void)hipFree(rd->mem);
+    if (rd->d_reg) (void)hipFree(rd->d_reg);
+    if (rd->h_reg) (void)hipHostFree(rd->h_reg);
+    if (rd->d_out) (void)hipFree(rd->d_out);
+    delete rd;
+}
+
+int reader_open(sccg_ctx* ctx, const uint8_t* d_rfa, int64_t rn, const uint8_t* d_rec, int64_t n, sccg_reader** out) {
+    sccg_reader* rd = new sccg_reader();
+    rd->ctx = ctx;
+    const int rc = reader_open_impl(ctx, d_rfa, rn, d_rec, n, rd);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);   // (nothing of the failed open is still queued)
+        reader_free(rd);
+        return rc;
+    }
+    *out = rd;
+    return SCCG_OK;
+}
+
+// the regions' total length after validating every one; SCCG_E_INVALID names the first bad region
+int fetch_check(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t* F) {
+    sccg_ctx* ctx = rd->ctx;
+    if (!regions && n) return ctx->fail(SCCG_E_INVALID, "null region list");
+    int64_t tot = 0;
+    for (size_t i = 0; i < n; i++) {
+        const int64_t b = regions[i].begin, e = regions[i].end;
+        if (b < 0 || e < b || e > rd->length)
+            return ctx->fail(SCCG_E_INVALID, "region %zu [%lld, %lld) is outside the sequence [0, %lld)", i, (long long)b,
+                             (long long)e, (long long)rd->length);
+        tot += e - b;
+    }
+    *F = tot;
+    return SCCG_OK;
+}
+
+// regions validated, F > 0, d_out holds F bytes: the region list in one copy, one launch, one sync
+int fetch_run(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t F, uint32_t flags, uint8_t* d_out,
+              hipStream_t s) {
+    sccg_ctx* ctx = rd->ctx;
+    const size_t words = 2 * n + 1, bytes = words * sizeof(int64_t);
+    if (rd->reg_cap < bytes) {
+        const size_t cap = bytes + bytes / 2 + 4096;
+        if (rd->d_reg) (void)hipFree(rd->d_reg);
+        if (rd->h_reg) (void)hipHostFree(rd->h_reg);
+        rd->d_reg = nullptr;
+        rd->h_reg = nullptr;
+        rd->reg_cap = 0;
+        hipError_t e = hipMalloc(&rd->d_reg, cap);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&rd->h_reg), cap, hipHostMallocDefault);
+        if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
+        rd->reg_cap = cap;
+    }
+    // [0, n]: exclusive prefix of the lengths (the flat output space -> region), (n, 2n]: begins
+    int64_t* h = rd->h_reg;
+    int64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        h[i] = at;
+        h[n + 1 + i] = regions[i].begin;
+        at += regions[i].end - regions[i].begin;
+    }
+    h[n] = at;
+    int64_t* d = reinterpret_cast<int64_t*>(rd->d_reg);
+    HIPTRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+    TRY(dc_fetch(rd->src, d, d + n + 1, (int64_t)n, F, (flags & SCCG_FETCH_UPPER) != 0, d_out, s));
+    HIPTRY(hipStreamSynchronize(s));
     return SCCG_OK;
 }
 
@@ -1402,6 +1630,85 @@ int sccg_reconstruct(sccg_ctx* ctx, const char* ref_fa, size_t ref_len, const ch
     h[len] = 0;
     out_fa->data = h;
     out_fa->len = (size_t)len;
+    return SCCG_OK;
+}
+
+int sccg_reader_open_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_len, const void* d_rec, size_t rec_len,
+                            sccg_reader** out, void* stream) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (!d_ref_fa && ref_len) || (!d_rec && rec_len)) return SCCG_E_INVALID;
+    HIPTRY(hipSetDevice(ctx->device));
+    hipStream_t saved = ctx->stream;
+    if (stream) ctx->stream = (hipStream_t)stream;
+    const int rc = reader_open(ctx, (const uint8_t*)d_ref_fa, (int64_t)ref_len, (const uint8_t*)d_rec, (int64_t)rec_len, out);
+    ctx->stream = saved;
+    return rc;
+}
+
+int sccg_reader_open(sccg_ctx* ctx, const char* ref_fa, size_t ref_len, const char* rec_text, size_t rec_len,
+                     sccg_reader** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (!ref_fa && ref_len) || (!rec_text && rec_len)) return SCCG_E_INVALID;
+    HIPTRY(hipSetDevice(ctx->device));
+    uint8_t* drf = reinterpret_cast<uint8_t*>(ctx->get(B_RFA, ref_len + 16));
+    uint8_t* drc = reinterpret_cast<uint8_t*>(ctx->get(B_TFA, rec_len + 16));
+    if (!drf || !drc) return ctx->fail(SCCG_E_NOMEM, "device allocation failed");
+    if (ref_len) HIPTRY(hipMemcpyAsync(drf, ref_fa, ref_len, hipMemcpyHostToDevice, ctx->stream));
+    if (rec_len) HIPTRY(hipMemcpyAsync(drc, rec_text, rec_len, hipMemcpyHostToDevice, ctx->stream));
+    return reader_open(ctx, drf, (int64_t)ref_len, drc, (int64_t)rec_len, out);
+}
+
+void sccg_reader_close(sccg_reader* reader) { reader_free(reader); }
+
+int64_t sccg_reader_length(const sccg_reader* reader) { return reader ? reader->length : -1; }
+
+const char* sccg_reader_header(const sccg_reader* reader, size_t* len) {
+    if (len) *len = reader ? reader->header.size() : 0;
+    return reader ? reader->header.c_str() : "";
+}
+
+int sccg_reader_fetch_device(sccg_reader* reader, const sccg_region* regions, size_t n, uint32_t flags, void* d_out,
+                             size_t out_cap, size_t* out_len, void* stream) {
+    if (!reader || !out_len) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    int64_t F = 0;
+    const int rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;
+    *out_len = (size_t)F;
+    if (!d_out) return SCCG_OK;   // size query
+    if ((size_t)F > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %lld bytes", (long long)F);
+    if (F == 0) return SCCG_OK;
+    HIPTRY(hipSetDevice(ctx->device));
+    return fetch_run(reader, regions, n, F, flags, (uint8_t*)d_out, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sccg_reader_fetch(sccg_reader* reader, const sccg_region* regions, size_t n, uint32_t flags, sccg_buf* out) {
+    if (!reader || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    int64_t F = 0;
+    int rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;   // (nothing written: *out is the caller's as it was)
+    char* h = (char*)malloc((size_t)F + 1);
+    if (!h) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
+    if (F > 0) {
+        HIPTRY(hipSetDevice(ctx->device));
+        if (reader->out_cap < (size_t)F + 16) {   // the reader's own output buffer, grown on demand
+            if (reader->d_out) (void)hipFree(reader->d_out);
+            reader->d_out = nullptr;
+            reader->out_cap = 0;
+            const size_t cap = (size_t)F + (size_t)F / 4 + 4096;
+            const hipError_t e = hipMalloc(&reader->d_out, cap);
+            if (e != hipSuccess) { free(h); reader->d_out = nullptr; return reader_alloc_fail(ctx, e, cap); }
+            reader->out_cap = cap;
+        }
+        rc = fetch_run(reader, regions, n, F, flags, (uint8_t*)reader->d_out, ctx->stream);
+        if (rc) { free(h); return rc; }
+        const hipError_t e = hipMemcpy(h, reader->d_out, (size_t)F, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { free(h); return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__)); }
+    }
+    h[F] = 0;
+    out->data = h;
+    out->len = (size_t)F;
     return SCCG_OK;
 }
 

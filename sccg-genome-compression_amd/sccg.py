@@ -19,6 +19,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "sccg.h")
 SCCG_OK = 0
 SCCG_E_DELTA_STOI = 4
 OPT_EXACT_SWITCH = 1   # sccg_ctx_set_option (include/sccg.h)
+FETCH_UPPER = 1        # sccg_reader_fetch flags
 ERRORS = {1: "SCCG_E_INVALID", 2: "SCCG_E_HIP", 3: "SCCG_E_NOMEM", 4: "SCCG_E_DELTA_STOI",
           5: "SCCG_E_FORMAT", 6: "SCCG_E_RANGE", 7: "SCCG_E_PARSE", 8: "SCCG_E_UNSUPPORTED",
           9: "SCCG_E_INTERNAL", 10: "SCCG_E_OPEN_REF", 11: "SCCG_E_OPEN_TGT", 12: "SCCG_E_WRITE"}
@@ -51,6 +52,11 @@ class Stats(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class Region(ctypes.Structure):
+    """sccg_region: 0-based, half-open sequence positions."""
+    _fields_ = [("begin", ctypes.c_int64), ("end", ctypes.c_int64)]
 
 
 class Params(ctypes.Structure):
@@ -124,6 +130,18 @@ def load_library():
     lib.sccg_reconstruct.argtypes = [vp, c, sz, c, sz, ctypes.POINTER(Buf)]
     lib.sccg_reconstruct_device.argtypes = [vp, vp, sz, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
     lib.sccg_buf_free.argtypes = [ctypes.POINTER(Buf)]
+    if hasattr(lib, "sccg_reader_open"):   # (absent from builds older than the region reader: A/B runs)
+        lib.sccg_reader_open.argtypes = [vp, c, sz, c, sz, ctypes.POINTER(vp)]
+        lib.sccg_reader_open_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(vp), vp]
+        lib.sccg_reader_close.argtypes = [vp]
+        lib.sccg_reader_close.restype = None
+        lib.sccg_reader_length.argtypes = [vp]
+        lib.sccg_reader_length.restype = i64
+        lib.sccg_reader_header.argtypes = [vp, ctypes.POINTER(sz)]
+        lib.sccg_reader_header.restype = vp
+        lib.sccg_reader_fetch.argtypes = [vp, ctypes.POINTER(Region), sz, ctypes.c_uint32, ctypes.POINTER(Buf)]
+        lib.sccg_reader_fetch_device.argtypes = [vp, ctypes.POINTER(Region), sz, ctypes.c_uint32, vp, sz,
+                                                 ctypes.POINTER(sz), vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -136,7 +154,7 @@ def load_library():
 def header_functions() -> list[str]:
     """Every function the C ABI header declares."""
     text = open(HEADER).read()
-    return sorted(set(re.findall(r"^\s*(?:int|void|size_t|const char\*)\s+(sccg_\w+)\s*\(", text, re.M)))
+    return sorted(set(re.findall(r"^\s*(?:int|void|size_t|int64_t|const char\*)\s+(sccg_\w+)\s*\(", text, re.M)))
 
 
 class Context:
@@ -258,6 +276,24 @@ class Context:
             self._err(rc)
         return n.value
 
+    def open_reader(self, record: bytes, ref_fa: bytes) -> "Reader":
+        """A region reader over a record (sccg_reader_open): the one-time work of reconstruct, kept.
+        Raises what reconstruct raises for the same bytes."""
+        ptr = ctypes.c_void_p()
+        rc = self.lib.sccg_reader_open(self.ptr, ref_fa, len(ref_fa), record, len(record), ctypes.byref(ptr))
+        if rc:
+            self._err(rc)
+        return Reader(self, ptr)
+
+    def open_reader_device(self, d_ref: int, ref_len: int, d_rec: int, rec_len: int, stream: int = 0) -> "Reader":
+        """open_reader on device-resident inputs (sccg_reader_open_device)."""
+        ptr = ctypes.c_void_p()
+        rc = self.lib.sccg_reader_open_device(self.ptr, d_ref, ref_len, d_rec, rec_len, ctypes.byref(ptr),
+                                              stream or None)
+        if rc:
+            self._err(rc)
+        return Reader(self, ptr)
+
     def profile(self, enable: bool = True, families: list | None = None) -> None:
         """Reset and enable (or disable) per-kernel HIP-event timing; `families` (names from
         sccg_profile_name) limits the bracketed launches to those families."""
@@ -330,3 +366,68 @@ class Context:
         out = [(recs.kind[i], recs.pos[i] if recs.kind[i] else 0, recs.len[i], recs.t[i]) for i in range(recs.n)]
         self.lib.sccg_records_free(ctypes.byref(recs))
         return out
+
+
+class Reader:
+    """sccg_reader: ranges of the target read from a record without rebuilding it.  It owns its
+    device memory (independent of later calls on the context); close it before the context."""
+
+    def __init__(self, ctx: Context, ptr: ctypes.c_void_p):
+        self.ctx, self.lib, self.ptr = ctx, ctx.lib, ptr
+
+    def close(self):
+        if self.ptr:
+            self.lib.sccg_reader_close(self.ptr)
+            self.ptr = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def length(self) -> int:
+        """Bases in the sequence (the FASTA body without its line ends)."""
+        return self.lib.sccg_reader_length(self.ptr)
+
+    @property
+    def header(self) -> bytes:
+        """The record's header line ('>' included) without its line end; b"" when it has none."""
+        n = ctypes.c_size_t()
+        p = self.lib.sccg_reader_header(self.ptr, ctypes.byref(n))
+        return ctypes.string_at(p, n.value) if n.value else b""
+
+    @staticmethod
+    def _regions(regions):
+        regions = list(regions)
+        arr = (Region * len(regions))(*[(int(b), int(e)) for b, e in regions]) if regions else None
+        return regions, arr
+
+    def fetch(self, regions, upper: bool = False) -> list[bytes]:
+        """One bytes object per (begin, end) pair (0-based, half-open), from one batched call."""
+        regions, arr = self._regions(regions)
+        buf = Buf()
+        rc = self.lib.sccg_reader_fetch(self.ptr, arr, len(regions), FETCH_UPPER if upper else 0, ctypes.byref(buf))
+        if rc:
+            self.ctx._err(rc)
+        data = self.ctx._take(buf)
+        out, at = [], 0
+        for b, e in regions:
+            out.append(data[at:at + (e - b)])
+            at += e - b
+        return out
+
+    def fetch_device(self, regions, d_out: int, out_cap: int, upper: bool = False, stream: int = 0) -> int:
+        """The regions' bases concatenated into device memory d_out (capacity out_cap); returns their
+        length.  d_out = 0 is a size query; a capacity too small raises SCCG_E_NOMEM with the size
+        needed in the error's `needed`."""
+        regions, arr = self._regions(regions)
+        n = ctypes.c_size_t()
+        rc = self.lib.sccg_reader_fetch_device(self.ptr, arr, len(regions), FETCH_UPPER if upper else 0,
+                                               d_out or None, out_cap, ctypes.byref(n), stream or None)
+        if rc:
+            err = SccgError(rc, self.lib.sccg_last_error(self.ctx.ptr).decode(errors="replace"))
+            err.needed = n.value
+            raise err
+        return n.value

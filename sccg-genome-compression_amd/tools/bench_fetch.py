@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Region-fetch times on the chr1-sized synthetic pair, beside the full reconstruction.
+
+    python bench_fetch.py [--profile hg --ref-len 247249719 --tgt-len 249250621 --seed 1] [--calls 20] [--warmup 3]
+Compresses the pair once, opens a reader on the device-resident record (open ms: host clock around
+sccg_reader_open_device, which ends in a synchronise) and times sccg_reader_fetch_device for
+1 x 1 kb, 1 x 1 Mb, 1000 x 1 kb and 100,000 x 100 b (seeded random starts): HIP events on the
+stream around each call (the region list's copy, the kernel and the call's own host work between
+them), the host clock around the same call, and -- in calls of their own -- the kernel alone from
+the profiler's "fetch" family.  sccg_reconstruct_device on the same pair in the same process is the
+yardstick.  Every shape's bytes are checked against the target FASTA.  Prints one JSON line
+(median, min, max of `calls` calls after `warmup`)."""
+import argparse
+import ctypes
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def spread(ts):
+    return {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--profile", default="hg")
+    ap.add_argument("--ref-len", type=int, default=247_249_719)
+    ap.add_argument("--tgt-len", type=int, default=249_250_621)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    import torch
+    import sccg
+    import synth
+    dev = torch.device("cuda", 0)
+    torch.zeros(1, device=dev)
+    rfa, tfa = synth.synth_pair(a.profile, a.ref_len, a.tgt_len, a.seed)
+    truth = tfa.partition(b"\n")[2].replace(b"\n", b"")
+    ctx = sccg.Context(0)
+    lib = ctx.lib
+    rec_h = ctx.compress(rfa, tfa)
+    d_ref = torch.frombuffer(bytearray(rfa), dtype=torch.uint8).to(dev)
+    d_rec = torch.frombuffer(bytearray(rec_h), dtype=torch.uint8).to(dev)
+    stream = torch.cuda.current_stream(dev)
+    s = stream.cuda_stream
+
+    def timed(call):
+        """(event ms, host ms) of `calls` calls after `warmup`"""
+        ev, host = [], []
+        for i in range(a.warmup + a.calls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            stream.synchronize()
+            t0 = time.perf_counter()
+            e0.record(stream)
+            call()
+            e1.record(stream)
+            stream.synchronize()
+            t1 = time.perf_counter()
+            if i >= a.warmup:
+                ev.append(e0.elapsed_time(e1))
+                host.append((t1 - t0) * 1e3)
+        return ev, host
+
+    # ---- yardstick: the full reconstruction
+    need = ctx.reconstruct_device(d_ref.data_ptr(), len(rfa), d_rec.data_ptr(), len(rec_h), 0, 0, s)
+    d_fa = torch.empty(need + 64, dtype=torch.uint8, device=dev)
+    ev, host = timed(lambda: ctx.reconstruct_device(d_ref.data_ptr(), len(rfa), d_rec.data_ptr(), len(rec_h),
+                                                    d_fa.data_ptr(), need + 64, s))
+    out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
+           "reconstruct_device": {"event_ms": spread(ev), "host_ms": spread(host), "out_bytes": need}}
+    del d_fa
+
+    # ---- open
+    opens = []
+    rd = None
+    for _ in range(3):
+        if rd is not None:
+            rd.close()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rd = ctx.open_reader_device(d_ref.data_ptr(), len(rfa), d_rec.data_ptr(), len(rec_h), s)
+        opens.append((time.perf_counter() - t0) * 1e3)
+    out["open_ms"] = spread(opens)
+    L = rd.length
+    assert L == len(truth)
+
+    # ---- fetch shapes
+    rng = random.Random(1)
+    shapes = {"1x1kb": (1, 1000), "1x1Mb": (1, 1_000_000), "1000x1kb": (1000, 1000), "100000x100b": (100_000, 100)}
+    out["fetch"] = {}
+    for name, (n, ln) in shapes.items():
+        begins = [rng.randrange(L - ln) for _ in range(n)]
+        arr = (sccg.Region * n)(*[(b, b + ln) for b in begins])
+        F = n * ln
+        d_o = torch.empty(F + 64, dtype=torch.uint8, device=dev)
+        got = ctypes.c_size_t()
+
+        def call():
+            rc = lib.sccg_reader_fetch_device(rd.ptr, arr, n, 0, d_o.data_ptr(), F, ctypes.byref(got), s)
+            assert rc == 0 and got.value == F, (rc, got.value)
+
+        ev, host = timed(call)
+        ctx.profile(True, families=["fetch"])
+        for _ in range(a.calls):
+            call()
+        kern = ctx.profile_get().get("fetch", (0.0, 0))
+        ctx.profile(False)
+        exact = d_o[:F].cpu().numpy().tobytes() == b"".join(truth[b:b + ln] for b in begins)
+        out["fetch"][name] = {"bytes": F, "event_ms": spread(ev), "host_ms": spread(host),
+                              "kernel_ms_mean": round(kern[0] / max(kern[1], 1), 4),
+                              "launches_per_call": kern[1] / a.calls, "exact": exact}
+        del d_o
+    rd.close()
+    ctx.close()
+    print(json.dumps(out))
+    if not all(v["exact"] for v in out["fetch"].values()):
+        raise SystemExit("bench_fetch: fetched bytes differ from the target FASTA")
+
+
+if __name__ == "__main__":
+    main()
