@@ -24,6 +24,8 @@
  * sccg_reader_fetch / _device         ranges of its `result`             decompression.cpp:241-262
  *   (sccg_reader_close, _length,        (no counterpart: the reference rebuilds the whole file)
  *    _header)
+ * sccg_reader_fetch_encoded / _device  the same ranges as base indices or one-hot elements, either
+ *   (sccg_fetch_bytes_per_base)         strand (no counterpart)
  *
  * Conventions: status ints (0 = OK); the library never calls exit(); host buffers it returns are
  * malloc'ed and released with sccg_buf_free.  One context per GPU; a context is not re-entrant;
@@ -228,6 +230,51 @@ const char* sccg_reader_header(const sccg_reader* reader, size_t* len); /* the r
 int sccg_reader_fetch(sccg_reader* reader, const sccg_region* regions, size_t n, uint32_t flags, sccg_buf* out);
 int sccg_reader_fetch_device(sccg_reader* reader, const sccg_region* regions /*host*/, size_t n, uint32_t flags,
                              void* d_out, size_t out_cap, size_t* out_len, void* stream);
+
+/* Encoded fetch: the same regions as ASCII, base indices or one-hot elements, each on either strand.
+ * Region i takes bytes_per_base * (end_i - begin_i) bytes at bytes_per_base * sum_{k<i}(end_k -
+ * begin_k), no separators; overlapping, repeated, empty and unordered regions and n == 0 as in
+ * sccg_reader_fetch.
+ *
+ *   encoding          dtype   bytes per base   a base's bytes
+ *   ----------------  ------  ---------------  -----------------------------------------------------
+ *   SCCG_ENC_ASCII    U8       1               the sequence byte (sccg_reader_fetch's)
+ *   SCCG_ENC_INDEX    U8       1               A/a 0, C/c 1, G/g 2, T/t 3, every other byte 4
+ *   SCCG_ENC_ONEHOT   U8       4               four elements (A, C, G, T): the base's is 1, the others
+ *                     F16      8               0; four zeros for a byte that is not ACGTacgt.  1 is
+ *                     BF16     8               0x01 / 0x3C00 / 0x3F80 / 0x3F800000
+ *                     F32     16
+ *
+ * Region i is on the reverse strand when strand[i] != 0 (strand: n host bytes, NULL = none) or when
+ * SCCG_FETCH_REVCOMP is set (all of them; with both it is still reversed): output base q is sequence
+ * position end - 1 - q, complemented.  ASCII complement, case kept: A<->T C<->G R<->Y K<->M B<->V D<->H;
+ * S, W, N and every other byte unchanged.  INDEX: 3 - code for codes 0-3, 4 stays; ONEHOT: the same on
+ * the channel.  INDEX and ONEHOT are case-blind and never read the lowercase runs; SCCG_FETCH_UPPER
+ * acts on ASCII and is accepted and ignored for the others.  ASCII with no strand and no REVCOMP is
+ * byte for byte sccg_reader_fetch.
+ *
+ * SCCG_E_INVALID, nothing written: a NULL reader / format / output, an unknown encoding or dtype, a
+ * dtype other than U8 with ASCII or INDEX, an unknown flag bit, reserved != 0, d_out not aligned to
+ * the element size, or a bad region (sccg_last_error names the first).  d_out == NULL is a size query;
+ * out_cap (bytes) too small returns SCCG_E_NOMEM with *out_len = the bytes needed.  One copy of the
+ * region list (the strands in it) and one kernel launch per call whatever n is; both forms
+ * synchronise before returning. */
+#define SCCG_ENC_ASCII   0u
+#define SCCG_ENC_INDEX   1u
+#define SCCG_ENC_ONEHOT  2u
+#define SCCG_DT_U8   0u
+#define SCCG_DT_F16  1u
+#define SCCG_DT_BF16 2u
+#define SCCG_DT_F32  3u   /* ONEHOT's element type; must be SCCG_DT_U8 for ASCII and INDEX */
+#define SCCG_FETCH_REVCOMP 2u   /* every region on the reverse strand */
+typedef struct { uint32_t encoding, dtype, flags, reserved /* 0 */; } sccg_fetch_format;
+
+size_t sccg_fetch_bytes_per_base(const sccg_fetch_format* fmt);   /* 1, 1, 4, 8, 8, 16; 0 = invalid format */
+int sccg_reader_fetch_encoded(sccg_reader* reader, const sccg_region* regions, size_t n, const uint8_t* strand,
+                              const sccg_fetch_format* fmt, sccg_buf* out);
+int sccg_reader_fetch_encoded_device(sccg_reader* reader, const sccg_region* regions /*host*/, size_t n,
+                                     const uint8_t* strand, const sccg_fetch_format* fmt, void* d_out,
+                                     size_t out_cap /*bytes*/, size_t* out_len /*bytes*/, void* stream);
 
 void sccg_buf_free(sccg_buf* b);
 

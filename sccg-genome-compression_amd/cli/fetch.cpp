@@ -3,8 +3,10 @@
 // `begin-end`, 1-based and inclusive as in `samtools faidx`, or a bare `pos` (one base).  Per region
 // it prints `>name:begin-end` (name: the record's header line without its '>', `seq` when it has
 // none) and the bases wrapped at 50 columns (decompression.cpp:266-274's width).  All regions go in
-// one sccg_reader_fetch call.  Exit code 1 on usage / region / open / format errors; the regions
-// are parsed before the GPU is touched.
+// one sccg_reader_fetch call.  `fetch -i <record_file> <reference_file> <region>...` (also
+// --reverse-complement; recognised as the first argument only) prints every region reverse-
+// complemented, as `samtools faidx -i` does, with `/rc` appended to its header line.  Exit code 1 on
+// usage / region / open / format errors; the regions are parsed before the GPU is touched.
 #include "cli_common.h"
 
 // decimal digits only, no sign, fits int64
@@ -20,14 +22,17 @@ static bool parse_pos(const std::string& s, int64_t* v) {
 }
 
 int main(int argc, char* argv[]) {
-    if (argc < 4) {
-        std::cerr << "Usage: " << argv[0] << " <record_file> <reference_file> <region>...\n"
-                  << "  region: begin-end (1-based, inclusive) or pos\n";
+    const bool rc_flag = argc > 1 && (std::string(argv[1]) == "-i" || std::string(argv[1]) == "--reverse-complement");
+    const int a0 = rc_flag ? 2 : 1;   // the first file argument
+    if (argc < a0 + 3) {
+        std::cerr << "Usage: " << argv[0] << " [-i] <record_file> <reference_file> <region>...\n"
+                  << "  region: begin-end (1-based, inclusive) or pos\n"
+                  << "  -i, --reverse-complement (first argument only): every region reverse-complemented\n";
         return 1;
     }
-    const std::string rec_path = argv[1], ref_path = argv[2];
+    const std::string rec_path = argv[a0], ref_path = argv[a0 + 1];
     std::vector<sccg_region> regions;
-    for (int i = 3; i < argc; i++) {
+    for (int i = a0 + 2; i < argc; i++) {
         const std::string a = argv[i];
         const size_t dash = a.find('-');
         int64_t b = 0, e = 0;
@@ -62,7 +67,12 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     sccg_buf seq{};
-    rc = sccg_reader_fetch(rd, regions.data(), regions.size(), 0, &seq);
+    if (rc_flag) {
+        const sccg_fetch_format fmt{SCCG_ENC_ASCII, SCCG_DT_U8, SCCG_FETCH_REVCOMP, 0};
+        rc = sccg_reader_fetch_encoded(rd, regions.data(), regions.size(), nullptr, &fmt, &seq);
+    } else {
+        rc = sccg_reader_fetch(rd, regions.data(), regions.size(), 0, &seq);
+    }
     if (rc) {
         std::cerr << "Error fetching: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
         sccg_reader_close(rd);
@@ -75,7 +85,7 @@ int main(int argc, char* argv[]) {
     std::string out;
     size_t at = 0;
     for (const sccg_region& r : regions) {
-        out += ">" + name + ":" + std::to_string(r.begin + 1) + "-" + std::to_string(r.end) + "\n";
+        out += ">" + name + ":" + std::to_string(r.begin + 1) + "-" + std::to_string(r.end) + (rc_flag ? "/rc\n" : "\n");
         const size_t len = (size_t)(r.end - r.begin);
         for (size_t k = 0; k < len; k += 50) {
             out.append(seq.data + at + k, len - k < 50 ? len - k : 50);

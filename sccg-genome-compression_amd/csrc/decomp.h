@@ -75,3 +75,9 @@ struct DcFetchSrc {
 // One launch whatever nreg is; regions and tokens were validated by the caller.
 int dc_fetch(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, bool upper,
              uint8_t* d_out, hipStream_t s);
+// The same regions encoded (enc: SCCG_ENC_*, dt: SCCG_DT_*, a valid pair): d_out[0, bytes_per_base * F),
+// base-major.  Region i is on the reverse strand (position end - 1 - q at output base q, complemented)
+// when bit 63 of d_beg[i] is set or all_rev; upper matters for ASCII only.  d_out aligned to the
+// element size.  One launch, under the same profiler family as dc_fetch.
+int dc_fetch_encoded(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, int enc, int dt,
+                     bool upper, bool all_rev, uint8_t* d_out, hipStream_t s);

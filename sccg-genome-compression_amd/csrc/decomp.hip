@@ -957,6 +957,92 @@ __device__ __forceinline__ int64_t wave_first(int64_t a, int64_t b, P&& pred) {
     return t ? a + (__ffsll((long long)t) - 1) : b;
 }
 
+// A span's decode, shared by the fetch kernels: sequence positions [j0, j1) (j1 - j0 <= FT_W) ->
+// decoded offsets [d0, d1) over the N runs -> record blocks [b0, b1] over boff -> k_tok_fill2's parse
+// of those blocks with every copy clipped to [d0, d1) into the wave's tile sdec (decoded byte d at
+// sdec[d - d0]; st: the wave's 2 * TK_B staging bytes).  Returns the first N run ending after j0
+// and d0; the tile is complete (wave_sync) on return.
+struct FetchSpan {
+    int64_t rn0, d0;
+};
+__device__ __forceinline__ FetchSpan fetch_decode_span(const DcFetchSrc& S, int64_t j0, int64_t j1, uint8_t* sdec, uint8_t* st) {
+    const int lane = lane_id();
+    const uint8_t* __restrict__ rec = S.rec;
+    const int64_t n = S.nrec, nblk = (n + TK_B - 1) / TK_B;
+    const int64_t* __restrict__ boff = S.boff;
+    const int32_t* __restrict__ ns = S.nr.start;
+    const int32_t* __restrict__ nl = S.nr.len;
+    const int64_t* __restrict__ ncum = S.nr.cum;
+    const int64_t nn = S.nr.n;
+    // positions -> decoded offsets: the N positions before j0 and before j1
+    const int64_t rn0 = wave_first(0, nn, [&](int64_t m) { return (int64_t)ns[m] + nl[m] > j0; });
+    const int64_t rn1 = wave_first(rn0, nn, [&](int64_t m) { return (int64_t)ns[m] + nl[m] > j1; });
+    const int64_t d0 = j0 - n_before_at(ns, nl, ncum, nn, rn0, j0), d1 = j1 - n_before_at(ns, nl, ncum, nn, rn1, j1);
+    if (d1 > d0) {
+        // record blocks holding decoded bytes d0 and d1 - 1 (a block's bytes: [boff[b], boff[b + 1]))
+        const int64_t b0 = wave_first(1, nblk, [&](int64_t m) { return boff[m] > d0; }) - 1;
+        const int64_t b1 = wave_first(b0 + 1, nblk, [&](int64_t m) { return boff[m] >= d1; }) - 1;
+        for (int64_t b = b0; b <= b1; b++) {
+            // k_tok_fill2's parse of block b
+            const int64_t rb = b * TK_B, ri = rb + lane;
+            const uint8_t c = ri < n ? rec[ri] : (uint8_t)',';
+            wave_sync();   // (the staged bytes of the block before are no longer read)
+            st[lane] = c;
+            st[TK_B + lane] = ri + TK_B < n ? rec[ri + TK_B] : (uint8_t)0;
+            wave_sync();
+            const RlView v{st - RL_BEHIND, rb, n, TK_B};   // v.at(q) = st[q - rb]
+            const bool par = ri < n && (c == '(' || c == ')');
+            const unsigned long long pm = __ballot(par) & ((1ull << lane) - 1ull);
+            const bool inside = pm ? st[63 - __clzll((long long)pm)] == '(' : S.bin[b] != 0;
+            int64_t contrib = 0, d = 0;
+            bool tok = false;
+            if (ri < n) {
+                if (c == '(') {
+                    int64_t comma = -1, close = -1, l = 0;
+                    for (int64_t q = ri + 1; q < n && q < ri + 32; q++) {
+                        const uint8_t cq = v.at(q);
+                        if (cq == ',' && comma < 0) comma = q;
+                        if (cq == ')') { close = q; break; }
+                        if (cq == '(') break;
+                    }
+                    if (comma > 0 && close > comma && parse_int_v(v, ri + 1, comma, &d) &&
+                        parse_int_v(v, comma + 1, close, &l) && l >= 0) {
+                        tok = true;
+                        contrib = l;
+                    }
+                } else if (c == ')') {
+                    contrib = inside ? 0 : 1;
+                } else if (!inside) {
+                    contrib = 1;
+                }
+            }
+            const int64_t o = boff[b] + wave_incl_add(contrib) - contrib;
+            const int64_t p = S.bdsum[b] + wave_incl_add(d);   // running p, this token included
+            if (!tok && contrib == 1 && c != '(' && o >= d0 && o < d1) sdec[o - d0] = c;
+            unsigned long long tm = __ballot(tok && o < d1 && o + contrib > d0);
+            while (tm) {
+                const int j = __ffsll((long long)tm) - 1;   // (wave-uniform: the token's fields by readlane)
+                tm &= tm - 1;
+                const int64_t pj = readlane64(p, j), oj = readlane64(o, j), lj = readlane64(contrib, j);
+                const int64_t a = oj > d0 ? oj : d0, e = oj + lj < d1 ? oj + lj : d1;
+                const uint8_t* __restrict__ src = S.R + pj + (a - oj);   // not walked there from the token's start
+                uint8_t* dst = sdec + (a - d0);
+                const int cnt = (int)(e - a), k = lane * OPT;   // cnt <= FT_W: one 16-byte load per lane
+                if (k < cnt) {
+                    const uint4 x = load16u(src + k);   // (up to 15 bytes past the token: R' carries the slack)
+                    const uint32_t w4[4] = {x.x, x.y, x.z, x.w};
+                    const int m = cnt - k < OPT ? cnt - k : OPT;
+#pragma unroll
+                    for (int q = 0; q < OPT; q++)
+                        if (q < m) dst[k + q] = (uint8_t)(w4[q >> 2] >> (8 * (q & 3)));
+                }
+            }
+        }
+        wave_sync();
+    }
+    return FetchSpan{rn0, d0};
+}
+
 struct FetchArgs {
     DcFetchSrc S;
     const int64_t* pre;   // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
@@ -976,9 +1062,6 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch(const FetchArgs A) {
     int64_t f = base < 0 ? 0 : base;
     if (f >= fend) return;
     const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 output bytes
-    const uint8_t* __restrict__ rec = A.S.rec;
-    const int64_t n = A.S.nrec, nblk = (n + TK_B - 1) / TK_B;
-    const int64_t* __restrict__ boff = A.S.boff;
     const int32_t* __restrict__ ns = A.S.nr.start;
     const int32_t* __restrict__ nl = A.S.nr.len;
     const int64_t* __restrict__ ncum = A.S.nr.cum;
@@ -996,73 +1079,9 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch(const FetchArgs A) {
         }
         const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
         const int64_t j0 = A.beg[i] + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
-        // positions -> decoded offsets: the N positions before j0 and before j1
-        const int64_t rn0 = wave_first(0, nn, [&](int64_t m) { return (int64_t)ns[m] + nl[m] > j0; });
-        const int64_t rn1 = wave_first(rn0, nn, [&](int64_t m) { return (int64_t)ns[m] + nl[m] > j1; });
-        const int64_t d0 = j0 - n_before_at(ns, nl, ncum, nn, rn0, j0), d1 = j1 - n_before_at(ns, nl, ncum, nn, rn1, j1);
+        const FetchSpan sp = fetch_decode_span(A.S, j0, j1, sdec, st);
+        const int64_t rn0 = sp.rn0, d0 = sp.d0;
         const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
-        if (d1 > d0) {
-            // record blocks holding decoded bytes d0 and d1 - 1 (a block's bytes: [boff[b], boff[b + 1]))
-            const int64_t b0 = wave_first(1, nblk, [&](int64_t m) { return boff[m] > d0; }) - 1;
-            const int64_t b1 = wave_first(b0 + 1, nblk, [&](int64_t m) { return boff[m] >= d1; }) - 1;
-            for (int64_t b = b0; b <= b1; b++) {
-                // k_tok_fill2's parse of block b
-                const int64_t rb = b * TK_B, ri = rb + lane;
-                const uint8_t c = ri < n ? rec[ri] : (uint8_t)',';
-                wave_sync();   // (the staged bytes of the block before are no longer read)
-                st[lane] = c;
-                st[TK_B + lane] = ri + TK_B < n ? rec[ri + TK_B] : (uint8_t)0;
-                wave_sync();
-                const RlView v{st - RL_BEHIND, rb, n, TK_B};   // v.at(q) = st[q - rb]
-                const bool par = ri < n && (c == '(' || c == ')');
-                const unsigned long long pm = __ballot(par) & ((1ull << lane) - 1ull);
-                const bool inside = pm ? st[63 - __clzll((long long)pm)] == '(' : A.S.bin[b] != 0;
-                int64_t contrib = 0, d = 0;
-                bool tok = false;
-                if (ri < n) {
-                    if (c == '(') {
-                        int64_t comma = -1, close = -1, l = 0;
-                        for (int64_t q = ri + 1; q < n && q < ri + 32; q++) {
-                            const uint8_t cq = v.at(q);
-                            if (cq == ',' && comma < 0) comma = q;
-                            if (cq == ')') { close = q; break; }
-                            if (cq == '(') break;
-                        }
-                        if (comma > 0 && close > comma && parse_int_v(v, ri + 1, comma, &d) &&
-                            parse_int_v(v, comma + 1, close, &l) && l >= 0) {
-                            tok = true;
-                            contrib = l;
-                        }
-                    } else if (c == ')') {
-                        contrib = inside ? 0 : 1;
-                    } else if (!inside) {
-                        contrib = 1;
-                    }
-                }
-                const int64_t o = boff[b] + wave_incl_add(contrib) - contrib;
-                const int64_t p = A.S.bdsum[b] + wave_incl_add(d);   // running p, this token included
-                if (!tok && contrib == 1 && c != '(' && o >= d0 && o < d1) sdec[o - d0] = c;
-                unsigned long long tm = __ballot(tok && o < d1 && o + contrib > d0);
-                while (tm) {
-                    const int j = __ffsll((long long)tm) - 1;   // (wave-uniform: the token's fields by readlane)
-                    tm &= tm - 1;
-                    const int64_t pj = readlane64(p, j), oj = readlane64(o, j), lj = readlane64(contrib, j);
-                    const int64_t a = oj > d0 ? oj : d0, e = oj + lj < d1 ? oj + lj : d1;
-                    const uint8_t* __restrict__ src = A.S.R + pj + (a - oj);   // not walked there from the token's start
-                    uint8_t* dst = sdec + (a - d0);
-                    const int cnt = (int)(e - a), k = lane * OPT;   // cnt <= FT_W: one 16-byte load per lane
-                    if (k < cnt) {
-                        const uint4 x = load16u(src + k);   // (up to 15 bytes past the token: R' carries the slack)
-                        const uint32_t w4[4] = {x.x, x.y, x.z, x.w};
-                        const int m = cnt - k < OPT ? cnt - k : OPT;
-#pragma unroll
-                        for (int q = 0; q < OPT; q++)
-                            if (q < m) dst[k + q] = (uint8_t)(w4[q >> 2] >> (8 * (q & 3)));
-                    }
-                }
-            }
-            wave_sync();
-        }
         // the lane's bytes of this span: the formatter's per-byte walk over the runs, without the wrap
         const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
         if (ga < gb) {
@@ -1097,6 +1116,195 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch(const FetchArgs A) {
         }
         wave_sync();   // (the tile is read before the next span fills it)
         f = fe;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Encoded region fetch (sccg_reader_fetch_encoded): k_fetch's flat space counted in BASES -- a wave
+// owns FT_W bases, a block OB -- with the strand and the encoding as an epilogue.  A span of a
+// reversed region (bit 63 of its begin, or all_rev) is mapped to the forward interval [j0, j1) it
+// covers and decoded forward by fetch_decode_span; a lane walks its bases ascending in j and
+// writes each final byte (ASCII, complemented when reversed) or code (0-3, 4 = not ACGT; 3 - code
+// when reversed) at its OUTPUT place in a second LDS tile, `fin`, one byte per base.  When the
+// wave's spans are done it streams fin out in 16-byte pieces, piece q to lane q % 64, so every
+// store instruction of the wave writes 1 KiB contiguous whatever the regions' lengths are: a
+// piece holds 16 / 4 / 2 / 1 bases at 1 / 4 / 8 / 16 bytes per base, expanded from the codes in
+// registers.  Pieces cut by the tile's ends [max(base, 0), fend), and every piece when d_out is
+// not aligned to a whole base (elemwise), are stored element by element.  INDEX and ONEHOT are
+// case-blind: they are launched with nlr = 0 and never look at the lowercase runs.
+// ---------------------------------------------------------------------------------------------
+constexpr int FE_ASCII = 0, FE_INDEX = 1, FE_ONEHOT = 2;     // SCCG_ENC_*
+constexpr int FD_U8 = 0, FD_F16 = 1, FD_BF16 = 2, FD_F32 = 3;   // SCCG_DT_*
+
+// IUPAC complement of an uppercase letter as its index 0..25, 13 letters x 5 bits per word
+// (A<->T C<->G R<->Y K<->M B<->V D<->H; every other letter is its own)
+constexpr uint64_t comp_word(int half) {
+    const char* from = "ACGTRYKMBVDH";
+    const char* to = "TGCAYRMKVBHD";
+    uint64_t w = 0;
+    for (int i = 0; i < 13; i++) {
+        const int c = 13 * half + i;
+        int r = c;
+        for (int k = 0; k < 12; k++)
+            if (from[k] - 'A' == c) r = to[k] - 'A';
+        w |= (uint64_t)r << (5 * i);
+    }
+    return w;
+}
+constexpr uint64_t COMP_LO = comp_word(0), COMP_HI = comp_word(1);
+static_assert((COMP_LO & 31) == 'T' - 'A' && ((COMP_HI >> (5 * ('T' - 'N'))) & 31) == 0, "A <-> T");
+static_assert(((COMP_LO >> (5 * ('K' - 'A'))) & 31) == 'M' - 'A' && (COMP_HI & 31) == 'N' - 'A', "K -> M, N -> N");
+
+// the complement of a sequence byte, case kept; a byte that is no letter is unchanged
+__device__ __forceinline__ uint32_t comp_ascii(uint32_t c) {
+    const uint32_t idx = (c | 0x20u) - 'a';
+    if (idx >= 26u) return c;
+    const uint64_t w = idx < 13u ? COMP_LO : COMP_HI;
+    const uint32_t r = (uint32_t)(w >> (5u * (idx < 13u ? idx : idx - 13u))) & 31u;
+    return ('A' + r) | (c & 0x20u);
+}
+
+// A/a 0, C/c 1, G/g 2, T/t 3, every other byte 4
+__device__ __forceinline__ uint32_t base_code(uint32_t c) {
+    const uint32_t u = c & 0xDFu;
+    return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 4u;
+}
+
+struct FetchEncArgs {
+    DcFetchSrc S;
+    const int64_t* pre;   // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
+    const int64_t* beg;   // nreg: region begins, bit 63 set = reverse strand
+    int64_t nreg, F, o_first, nlr;   // o_first: the flat base of block 0's first base (<= 0)
+    uint32_t all_rev, elemwise;
+    uint8_t* out;
+};
+
+template <int ENC, int DT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_enc(const FetchEncArgs A) {
+    constexpr int ES = DT == FD_U8 ? 1 : DT == FD_F32 ? 4 : 2;   // element bytes
+    constexpr int BPB = ENC == FE_ONEHOT ? 4 * ES : 1;           // bytes per base
+    constexpr int PB = 16 / BPB;                                 // bases per 16-byte piece
+    constexpr uint32_t ONE = DT == FD_U8 ? 1u : DT == FD_F16 ? 0x3C00u : DT == FD_BF16 ? 0x3F80u : 0x3F800000u;
+    static_assert(ENC == FE_ONEHOT || DT == FD_U8, "ASCII and INDEX are bytes");
+    __shared__ uint8_t tile[WPB][FT_W];
+    __shared__ __attribute__((aligned(16))) uint8_t fin[WPB][FT_W];
+    __shared__ uint8_t stg[WPB][2 * TK_B];
+    const int lane = lane_id();
+    uint8_t* sdec = tile[wave_in_block()];
+    uint8_t* fw = fin[wave_in_block()];
+    uint8_t* st = stg[wave_in_block()];
+    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
+    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
+    const int64_t w0 = base < 0 ? 0 : base;
+    int64_t f = w0;
+    if (f >= fend) return;
+    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
+    const int32_t* __restrict__ ns = A.S.nr.start;
+    const int32_t* __restrict__ nl = A.S.nr.len;
+    const int64_t* __restrict__ ncum = A.S.nr.cum;
+    const int32_t* __restrict__ ls = A.S.lr.start;
+    const int32_t* __restrict__ ll = A.S.lr.len;
+    const int64_t nn = A.S.nr.n, nlr = ENC == FE_ASCII ? A.nlr : 0;
+    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
+    const int64_t* __restrict__ pre = A.pre;
+    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+    while (f < fend) {
+        if (pre[i + 1] <= f) {
+            i++;
+            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+        }
+        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
+        const int64_t braw = A.beg[i];
+        const bool rev = A.all_rev || braw < 0;
+        const int64_t bg = braw & INT64_MAX;
+        // reversed: flat base g of the region is position end - 1 - (g - pre[i]); [f, fe) covers [j0, j1)
+        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
+        const FetchSpan sp = fetch_decode_span(A.S, j0, j1, sdec, st);
+        const int64_t rn0 = sp.rn0, d0 = sp.d0;
+        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
+        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
+        if (ga < gb) {
+            // ascending in j; a reversed span's results land at descending places
+            int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f), rn = rn0, rl = rl0;
+            int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot, l_s = INT64_MAX, l_e = INT64_MAX;
+            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+            if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
+            const int k0 = (int)(ga - g0), k1 = (int)(gb - g0);
+            uint8_t* mine = fw + lane * OPT;
+            for (int t = 0; t < k1 - k0; t++) {
+                while (j >= n_e) {
+                    rn++;
+                    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+                    else { n_s = n_e = INT64_MAX; n_b = ntot; }
+                }
+                while (j >= l_e) {
+                    rl++;
+                    if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
+                    else l_s = l_e = INT64_MAX;
+                }
+                uint32_t c = j >= n_s ? (uint32_t)'N' : (uint32_t)sdec[j - n_b - d0];
+                if (ENC == FE_ASCII) {
+                    if (j >= l_s) c = c_tolower((uint8_t)c);
+                    if (rev) c = comp_ascii(c);
+                } else {
+                    c = base_code(c);
+                    if (rev && c < 4u) c = 3u - c;
+                }
+                j++;
+                mine[rev ? k1 - 1 - t : k0 + t] = (uint8_t)c;
+            }
+        }
+        wave_sync();   // (the tile is read before the next span fills it)
+        f = fe;
+    }
+    wave_sync();   // fin[w0 - base, fend - base) is complete
+    for (int it = 0; it < BPB; it++) {
+        const int q = it * 64 + lane;
+        const int64_t p0 = base + (int64_t)q * PB;   // the piece's first base
+        if (p0 >= fend || p0 + PB <= w0) continue;
+        const uint8_t* src = fw + q * PB;
+        uint8_t* dst = A.out + p0 * BPB;
+        const bool full = !A.elemwise && p0 >= w0 && p0 + PB <= fend;
+        if (BPB == 1) {
+            if (full) {
+                *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+            } else {
+                for (int t = 0; t < PB; t++)
+                    if (p0 + t >= w0 && p0 + t < fend) dst[t] = src[t];
+            }
+        } else {
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int t = 0; t < PB; t++) {
+                const uint32_t code = src[t];
+                if (ES == 1) {
+                    w[t] = code < 4u ? ONE << (8u * code) : 0u;
+                } else if (ES == 2) {
+                    const uint64_t v = code < 4u ? (uint64_t)ONE << (16u * code) : 0ull;
+                    w[2 * t] = (uint32_t)v;
+                    w[2 * t + 1] = (uint32_t)(v >> 32);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) w[e] = code == (uint32_t)e ? ONE : 0u;
+                }
+            }
+            if (full) {
+                *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < PB; t++) {
+                    if (p0 + t < w0 || p0 + t >= fend) continue;
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const int by = (t * 4 + e) * ES;   // the element's byte in the piece
+                        const uint32_t x = w[by >> 2] >> (8 * (by & 3));
+                        if (ES == 1) dst[by] = (uint8_t)x;
+                        else if (ES == 2) *reinterpret_cast<uint16_t*>(dst + by) = (uint16_t)x;
+                        else *reinterpret_cast<uint32_t*>(dst + by) = x;
+                    }
+                }
+            }
+        }
     }
 }
 
@@ -1296,6 +1504,29 @@ int dc_fetch(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, 
     FetchArgs A{src, d_pre, d_beg, nreg, F, -(int64_t)((uintptr_t)d_out & 15), upper ? 0 : src.lr.n, d_out};
     const int64_t nblk = (F - A.o_first + OB - 1) / OB;
     PROF_LAUNCH(PROF_FETCH, s, k_fetch, dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
+int dc_fetch_encoded(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, int enc, int dt,
+                     bool upper, bool all_rev, uint8_t* d_out, hipStream_t s) {
+    if (F <= 0) return 0;
+    const int es = dt == FD_U8 ? 1 : dt == FD_F32 ? 4 : 2, bpb = enc == FE_ONEHOT ? 4 * es : 1;
+    // whole bases per 16-byte piece need d_out on a base boundary; else every store is an element's
+    const bool elemwise = ((uintptr_t)d_out % (uintptr_t)bpb) != 0;
+    FetchEncArgs A{src, d_pre, d_beg, nreg, F, elemwise ? 0 : -(int64_t)(((uintptr_t)d_out & 15) / (uintptr_t)bpb),
+                   upper ? 0 : src.lr.n, all_rev ? 1u : 0u, elemwise ? 1u : 0u, d_out};
+    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
+#define SCCG_FETCH_ENC(E, D) \
+    PROF_LAUNCH(PROF_FETCH, s, (k_fetch_enc<E, D>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A)
+    if (enc == FE_ASCII && dt == FD_U8) SCCG_FETCH_ENC(FE_ASCII, FD_U8);
+    else if (enc == FE_INDEX && dt == FD_U8) SCCG_FETCH_ENC(FE_INDEX, FD_U8);
+    else if (enc == FE_ONEHOT && dt == FD_U8) SCCG_FETCH_ENC(FE_ONEHOT, FD_U8);
+    else if (enc == FE_ONEHOT && dt == FD_F16) SCCG_FETCH_ENC(FE_ONEHOT, FD_F16);
+    else if (enc == FE_ONEHOT && dt == FD_BF16) SCCG_FETCH_ENC(FE_ONEHOT, FD_BF16);
+    else if (enc == FE_ONEHOT && dt == FD_F32) SCCG_FETCH_ENC(FE_ONEHOT, FD_F32);
+    else return SCCG_E_INVALID;
+#undef SCCG_FETCH_ENC
     SCCG_HIP(hipGetLastError());
     return 0;
 }

@@ -1483,9 +1483,19 @@ int fetch_check(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t* 
     return SCCG_OK;
 }
 
-// regions validated, F > 0, d_out holds F bytes: the region list in one copy, one launch, one sync
+// the encoded fetch's format: 0 = invalid, else the bytes per base
+size_t fetch_format_bpb(const sccg_fetch_format* f) {
+    if (!f || f->reserved || (f->flags & ~(SCCG_FETCH_UPPER | SCCG_FETCH_REVCOMP))) return 0;
+    if (f->encoding == SCCG_ENC_ASCII || f->encoding == SCCG_ENC_INDEX) return f->dtype == SCCG_DT_U8 ? 1 : 0;
+    if (f->encoding != SCCG_ENC_ONEHOT) return 0;
+    return f->dtype == SCCG_DT_U8 ? 4 : f->dtype == SCCG_DT_F16 || f->dtype == SCCG_DT_BF16 ? 8 : f->dtype == SCCG_DT_F32 ? 16 : 0;
+}
+
+// regions validated, F > 0, d_out holds the output: the region list in one copy, one launch, one
+// sync.  fmt NULL: sccg_reader_fetch's bytes (k_fetch); else the encoded form, strand (may be NULL)
+// travelling as bit 63 of the begins
 int fetch_run(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t F, uint32_t flags, uint8_t* d_out,
-              hipStream_t s) {
+              hipStream_t s, const sccg_fetch_format* fmt = nullptr, const uint8_t* strand = nullptr) {
     sccg_ctx* ctx = rd->ctx;
     const size_t words = 2 * n + 1, bytes = words * sizeof(int64_t);
     if (rd->reg_cap < bytes) {
@@ -1505,13 +1515,17 @@ int fetch_run(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t F, 
     int64_t at = 0;
     for (size_t i = 0; i < n; i++) {
         h[i] = at;
-        h[n + 1 + i] = regions[i].begin;
+        h[n + 1 + i] = regions[i].begin | (strand && strand[i] ? INT64_MIN : 0);
         at += regions[i].end - regions[i].begin;
     }
     h[n] = at;
     int64_t* d = reinterpret_cast<int64_t*>(rd->d_reg);
     HIPTRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    TRY(dc_fetch(rd->src, d, d + n + 1, (int64_t)n, F, (flags & SCCG_FETCH_UPPER) != 0, d_out, s));
+    if (fmt)
+        TRY(dc_fetch_encoded(rd->src, d, d + n + 1, (int64_t)n, F, (int)fmt->encoding, (int)fmt->dtype,
+                             (flags & SCCG_FETCH_UPPER) != 0, (flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
+    else
+        TRY(dc_fetch(rd->src, d, d + n + 1, (int64_t)n, F, (flags & SCCG_FETCH_UPPER) != 0, d_out, s));
     HIPTRY(hipStreamSynchronize(s));
     return SCCG_OK;
 }
@@ -1709,6 +1723,63 @@ int sccg_reader_fetch(sccg_reader* reader, const sccg_region* regions, size_t n,
     h[F] = 0;
     out->data = h;
     out->len = (size_t)F;
+    return SCCG_OK;
+}
+
+size_t sccg_fetch_bytes_per_base(const sccg_fetch_format* fmt) { return fetch_format_bpb(fmt); }
+
+int sccg_reader_fetch_encoded_device(sccg_reader* reader, const sccg_region* regions, size_t n, const uint8_t* strand,
+                                     const sccg_fetch_format* fmt, void* d_out, size_t out_cap, size_t* out_len, void* stream) {
+    if (!reader || !fmt || !out_len) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    const size_t bpb = fetch_format_bpb(fmt);
+    if (!bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
+                               fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
+    const size_t es = fmt->encoding == SCCG_ENC_ONEHOT ? bpb / 4 : 1;
+    if ((uintptr_t)d_out % es) return ctx->fail(SCCG_E_INVALID, "d_out is not aligned to the %zu-byte element", es);
+    int64_t F = 0;
+    const int rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;
+    *out_len = (size_t)F * bpb;
+    if (!d_out) return SCCG_OK;   // size query
+    if ((size_t)F * bpb > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu bytes", (size_t)F * bpb);
+    if (F == 0) return SCCG_OK;
+    HIPTRY(hipSetDevice(ctx->device));
+    return fetch_run(reader, regions, n, F, fmt->flags, (uint8_t*)d_out, stream ? (hipStream_t)stream : ctx->stream, fmt, strand);
+}
+
+int sccg_reader_fetch_encoded(sccg_reader* reader, const sccg_region* regions, size_t n, const uint8_t* strand,
+                              const sccg_fetch_format* fmt, sccg_buf* out) {
+    if (!reader || !fmt || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    const size_t bpb = fetch_format_bpb(fmt);
+    if (!bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
+                               fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
+    int64_t F = 0;
+    int rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;   // (nothing written: *out is the caller's as it was)
+    const size_t bytes = (size_t)F * bpb;
+    char* h = (char*)malloc(bytes + 1);
+    if (!h) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
+    if (F > 0) {
+        HIPTRY(hipSetDevice(ctx->device));
+        if (reader->out_cap < bytes + 16) {   // the reader's own output buffer, grown on demand
+            if (reader->d_out) (void)hipFree(reader->d_out);
+            reader->d_out = nullptr;
+            reader->out_cap = 0;
+            const size_t cap = bytes + bytes / 4 + 4096;
+            const hipError_t e = hipMalloc(&reader->d_out, cap);
+            if (e != hipSuccess) { free(h); reader->d_out = nullptr; return reader_alloc_fail(ctx, e, cap); }
+            reader->out_cap = cap;
+        }
+        rc = fetch_run(reader, regions, n, F, fmt->flags, (uint8_t*)reader->d_out, ctx->stream, fmt, strand);
+        if (rc) { free(h); return rc; }
+        const hipError_t e = hipMemcpy(h, reader->d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { free(h); return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__)); }
+    }
+    h[bytes] = 0;
+    out->data = h;
+    out->len = bytes;
     return SCCG_OK;
 }
 

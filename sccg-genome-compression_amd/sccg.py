@@ -20,6 +20,9 @@ SCCG_OK = 0
 SCCG_E_DELTA_STOI = 4
 OPT_EXACT_SWITCH = 1   # sccg_ctx_set_option (include/sccg.h)
 FETCH_UPPER = 1        # sccg_reader_fetch flags
+FETCH_REVCOMP = 2      # sccg_reader_fetch_encoded: every region on the reverse strand
+ENCODINGS = {"ascii": 0, "index": 1, "onehot": 2}          # SCCG_ENC_*
+DTYPES = {"u8": 0, "f16": 1, "bf16": 2, "f32": 3}          # SCCG_DT_*
 ERRORS = {1: "SCCG_E_INVALID", 2: "SCCG_E_HIP", 3: "SCCG_E_NOMEM", 4: "SCCG_E_DELTA_STOI",
           5: "SCCG_E_FORMAT", 6: "SCCG_E_RANGE", 7: "SCCG_E_PARSE", 8: "SCCG_E_UNSUPPORTED",
           9: "SCCG_E_INTERNAL", 10: "SCCG_E_OPEN_REF", 11: "SCCG_E_OPEN_TGT", 12: "SCCG_E_WRITE"}
@@ -57,6 +60,12 @@ class Stats(ctypes.Structure):
 class Region(ctypes.Structure):
     """sccg_region: 0-based, half-open sequence positions."""
     _fields_ = [("begin", ctypes.c_int64), ("end", ctypes.c_int64)]
+
+
+class FetchFormat(ctypes.Structure):
+    """sccg_fetch_format: encoding (ENCODINGS), ONEHOT's element type (DTYPES), FETCH_* flags, 0."""
+    _fields_ = [("encoding", ctypes.c_uint32), ("dtype", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
 
 
 class Params(ctypes.Structure):
@@ -142,6 +151,13 @@ def load_library():
         lib.sccg_reader_fetch.argtypes = [vp, ctypes.POINTER(Region), sz, ctypes.c_uint32, ctypes.POINTER(Buf)]
         lib.sccg_reader_fetch_device.argtypes = [vp, ctypes.POINTER(Region), sz, ctypes.c_uint32, vp, sz,
                                                  ctypes.POINTER(sz), vp]
+    if hasattr(lib, "sccg_reader_fetch_encoded"):   # (absent from builds older than the encoded fetch: A/B runs)
+        lib.sccg_fetch_bytes_per_base.argtypes = [ctypes.POINTER(FetchFormat)]
+        lib.sccg_fetch_bytes_per_base.restype = sz
+        lib.sccg_reader_fetch_encoded.argtypes = [vp, ctypes.POINTER(Region), sz, c, ctypes.POINTER(FetchFormat),
+                                                  ctypes.POINTER(Buf)]
+        lib.sccg_reader_fetch_encoded_device.argtypes = [vp, ctypes.POINTER(Region), sz, c, ctypes.POINTER(FetchFormat),
+                                                         vp, sz, ctypes.POINTER(sz), vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -162,6 +178,7 @@ class Context:
 
     def __init__(self, device: int = 0):
         self.lib = load_library()
+        self.device = device
         self.ptr = ctypes.c_void_p()
         rc = self.lib.sccg_ctx_create(device, ctypes.byref(self.ptr))
         if rc:
@@ -431,3 +448,77 @@ class Reader:
             err.needed = n.value
             raise err
         return n.value
+
+    @staticmethod
+    def _format(encoding: str, dtype: str, revcomp: bool, upper: bool) -> FetchFormat:
+        if encoding not in ENCODINGS or dtype not in DTYPES:
+            raise ValueError(f"encoding {encoding!r} / dtype {dtype!r}: one of {sorted(ENCODINGS)} / {sorted(DTYPES)}")
+        return FetchFormat(ENCODINGS[encoding], DTYPES[dtype], (FETCH_UPPER if upper else 0) | (FETCH_REVCOMP if revcomp else 0), 0)
+
+    @staticmethod
+    def _strand(strand, n: int):
+        if strand is None:
+            return None
+        strand = bytes(1 if x else 0 for x in strand)
+        if len(strand) != n:
+            raise ValueError(f"{len(strand)} strands for {n} regions")
+        return strand or None
+
+    def fetch_encoded(self, regions, encoding: str = "index", dtype: str = "u8", strand=None, revcomp: bool = False,
+                      upper: bool = False) -> bytes:
+        """The regions' bases concatenated and encoded (sccg_reader_fetch_encoded): "ascii" and
+        "index" (A 0, C 1, G 2, T 3, other 4) one byte per base, "onehot" four `dtype` elements per
+        base.  strand: one truthy / falsy value per region, truthy = reverse complement; revcomp:
+        all of them."""
+        regions, arr = self._regions(regions)
+        fmt = self._format(encoding, dtype, revcomp, upper)
+        buf = Buf()
+        rc = self.lib.sccg_reader_fetch_encoded(self.ptr, arr, len(regions), self._strand(strand, len(regions)),
+                                                ctypes.byref(fmt), ctypes.byref(buf))
+        if rc:
+            self.ctx._err(rc)
+        return self.ctx._take(buf)
+
+    def fetch_encoded_device(self, regions, d_out: int, out_cap: int, encoding: str = "index", dtype: str = "u8", strand=None,
+                             revcomp: bool = False, upper: bool = False, stream: int = 0) -> int:
+        """fetch_encoded into device memory d_out (capacity out_cap bytes, aligned to the element);
+        returns the bytes written.  d_out = 0 is a size query; a capacity too small raises
+        SCCG_E_NOMEM with the bytes needed in the error's `needed`."""
+        regions, arr = self._regions(regions)
+        fmt = self._format(encoding, dtype, revcomp, upper)
+        n = ctypes.c_size_t()
+        rc = self.lib.sccg_reader_fetch_encoded_device(self.ptr, arr, len(regions), self._strand(strand, len(regions)),
+                                                       ctypes.byref(fmt), d_out or None, out_cap, ctypes.byref(n),
+                                                       stream or None)
+        if rc:
+            err = SccgError(rc, self.lib.sccg_last_error(self.ctx.ptr).decode(errors="replace"))
+            err.needed = n.value
+            raise err
+        return n.value
+
+    def fetch_tensor(self, regions, encoding: str = "onehot", dtype=None, strand=None, revcomp: bool = False, stream=None):
+        """A torch tensor on the context's device: [n, L] ("index", "ascii": uint8) or [n, L, 4]
+        ("onehot": dtype, default torch.float16) when every region has the same length L, else flat
+        [F] / [F, 4].  stream: a torch stream (default: the current one)."""
+        import torch
+        regions = [(int(b), int(e)) for b, e in regions]
+        names = {torch.uint8: "u8", torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32"}
+        if encoding != "onehot":
+            dtype = torch.uint8 if dtype is None else dtype
+            if dtype != torch.uint8:
+                raise ValueError(f"{encoding!r} is uint8")
+        elif dtype is None:
+            dtype = torch.float16
+        if dtype not in names:
+            raise ValueError(f"dtype {dtype}: one of {list(names)}")
+        dev = torch.device("cuda", self.ctx.device)
+        F = sum(e - b for b, e in regions)
+        shape = (F, 4) if encoding == "onehot" else (F,)
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        self.fetch_encoded_device(regions, out.data_ptr(), out.numel() * out.element_size(), encoding, names[dtype], strand,
+                                  revcomp, stream=s.cuda_stream)
+        lens = {e - b for b, e in regions}
+        if len(lens) == 1 and regions:
+            out = out.view(len(regions), lens.pop(), *shape[1:])
+        return out

@@ -8,7 +8,10 @@ sccg_reader_open_device, which ends in a synchronise) and times sccg_reader_fetc
 stream around each call (the region list's copy, the kernel and the call's own host work between
 them), the host clock around the same call, and -- in calls of their own -- the kernel alone from
 the profiler's "fetch" family.  sccg_reconstruct_device on the same pair in the same process is the
-yardstick.  Every shape's bytes are checked against the target FASTA.  Prints one JSON line
+yardstick.  Then sccg_reader_fetch_encoded_device at 1000 x 1 kb and 100,000 x 100 b -- index, one-hot
+f16 and f32, ASCII with alternating strands -- each beside the two-step path it replaces: the ASCII
+fetch of the same regions followed by a PyTorch lookup-table encode to the same dtype on the same
+stream.  Every shape's bytes are checked against the target FASTA.  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
 import ctypes
@@ -18,6 +21,8 @@ import random
 import statistics
 import sys
 import time
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -116,9 +121,80 @@ def main() -> None:
                               "kernel_ms_mean": round(kern[0] / max(kern[1], 1), 4),
                               "launches_per_call": kern[1] / a.calls, "exact": exact}
         del d_o
+    # ---- encoded fetch beside the two-step path (ASCII fetch, then a PyTorch lookup-table encode on
+    # the same stream): index, one-hot f16 / f32 on the forward strand, ASCII with alternating strands
+    comp = bytes.maketrans(b"ACGTRYKMBVDHacgtrykmbvdh", b"TGCAYRMKVBHDtgcayrmkvbhd")
+    code = [4] * 256
+    for k, ch in enumerate(b"ACGT"):
+        code[ch] = code[ch + 32] = k
+    lut_idx = torch.tensor(code, dtype=torch.uint8, device=dev)
+    lut_comp = torch.tensor(list(comp), dtype=torch.uint8, device=dev)
+    eye = torch.cat([torch.eye(4, device=dev), torch.zeros(1, 4, device=dev)])
+    rows = {"index": ("index", "u8", torch.uint8, 1), "onehot_f16": ("onehot", "f16", torch.float16, 8),
+            "onehot_f32": ("onehot", "f32", torch.float32, 16), "ascii_strands": ("ascii", "u8", torch.uint8, 1)}
+    out["fetch_encoded"] = {}
+    # (a library older than the encoded fetch, SCCG_LIB_PATH in A/B runs, has the rows above only)
+    enc_shapes = ("1000x1kb", "100000x100b") if hasattr(lib, "sccg_reader_fetch_encoded_device") else ()
+    for name, (n, ln) in {k: shapes[k] for k in enc_shapes}.items():
+        begins = [rng.randrange(L - ln) for _ in range(n)]
+        arr = (sccg.Region * n)(*[(b, b + ln) for b in begins])
+        F = n * ln
+        d_a = torch.empty(F + 64, dtype=torch.uint8, device=dev)
+        got = ctypes.c_size_t()
+        fwd = b"".join(truth[b:b + ln] for b in begins)
+        for row, (enc, dt, tdt, bpb) in rows.items():
+            strands = bytes(k & 1 for k in range(n)) if row == "ascii_strands" else None
+            fmt = sccg.FetchFormat(sccg.ENCODINGS[enc], sccg.DTYPES[dt], 0, 0)
+            d_o = torch.empty(F * bpb + 64, dtype=torch.uint8, device=dev)
+            table = None if enc == "ascii" else lut_idx if enc == "index" else eye[lut_idx.long()].to(tdt).contiguous()
+            two = [None]
+
+            def call():
+                rc = lib.sccg_reader_fetch_encoded_device(rd.ptr, arr, n, strands, ctypes.byref(fmt), d_o.data_ptr(), F * bpb,
+                                                          ctypes.byref(got), s)
+                assert rc == 0 and got.value == F * bpb, (rc, got.value)
+
+            def two_step():
+                rc = lib.sccg_reader_fetch_device(rd.ptr, arr, n, 0, d_a.data_ptr(), F, ctypes.byref(got), s)
+                assert rc == 0 and got.value == F, (rc, got.value)
+                a_ = d_a[:F]
+                if enc == "ascii":   # complement everything, then put the reversed rows back to front
+                    t = torch.where((torch.arange(n, device=dev) & 1).bool()[:, None], lut_comp[a_.int()].view(n, ln).flip(1),
+                                    a_.view(n, ln))
+                else:
+                    t = table[a_.int()]
+                two[0] = t
+
+            ev, host = timed(call)
+            ev2, host2 = timed(two_step)
+            ctx.profile(True, families=["fetch"])
+            for _ in range(a.calls):
+                call()
+            kern = ctx.profile_get().get("fetch", (0.0, 0))
+            ctx.profile(False)
+            if enc == "ascii":
+                want = b"".join(truth[b:b + ln].translate(comp)[::-1] if k & 1 else truth[b:b + ln] for k, b in enumerate(begins))
+            else:
+                c = np.array(code, dtype=np.uint8)[np.frombuffer(fwd, dtype=np.uint8)]
+                want = c.tobytes() if enc == "index" else np.vstack([np.eye(4), np.zeros((1, 4))]).astype(
+                    np.float16 if dt == "f16" else np.float32)[c].tobytes()
+            bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[two[0].element_size()]
+            exact = d_o[:F * bpb].cpu().numpy().tobytes() == want
+            exact2 = two[0].contiguous().view(bits).cpu().numpy().tobytes() == want
+            med, med2 = statistics.median(ev), statistics.median(ev2)
+            out["fetch_encoded"][f"{name}/{row}"] = {
+                "bytes": F * bpb, "event_ms": spread(ev), "host_ms": spread(host),
+                "kernel_ms_mean": round(kern[0] / max(kern[1], 1), 4), "launches_per_call": kern[1] / a.calls,
+                "out_GBps": round(F * bpb / med / 1e6, 1), "exact": exact,
+                "two_step_event_ms": spread(ev2), "two_step_host_ms": spread(host2), "two_step_exact": exact2,
+                "two_step_over_encoded": round(med2 / med, 2)}
+            del d_o
+        del d_a
     rd.close()
     ctx.close()
     print(json.dumps(out))
+    if not all(v["exact"] and v["two_step_exact"] for v in out["fetch_encoded"].values()):
+        raise SystemExit("bench_fetch: encoded bytes differ from the target FASTA")
     if not all(v["exact"] for v in out["fetch"].values()):
         raise SystemExit("bench_fetch: fetched bytes differ from the target FASTA")
 
