@@ -26,6 +26,14 @@
  *    _header)
  * sccg_reader_fetch_encoded / _device  the same ranges as base indices or one-hot elements, either
  *   (sccg_fetch_bytes_per_base)         strand (no counterpart)
+ * sccg_reference_open / _device       the reference strip alone, kept     decompression.cpp:105-110
+ *   (sccg_reference_close,              and shared: sccg_reader_open without the strip and without a
+ *    _device_bytes, sccg_reader_open_   private R' (no counterpart: the reference strips per run)
+ *    shared / _device, sccg_reader_
+ *    device_bytes)
+ * sccg_cohort_create / _fetch /       the encoded fetch over many records of one context, each region
+ *   _fetch_device (sccg_cohort_close,   naming its record, in one launch (no counterpart)
+ *    _samples)
  *
  * Conventions: status ints (0 = OK); the library never calls exit(); host buffers it returns are
  * malloc'ed and released with sccg_buf_free.  One context per GPU; a context is not re-entrant;
@@ -275,6 +283,76 @@ int sccg_reader_fetch_encoded(sccg_reader* reader, const sccg_region* regions, s
 int sccg_reader_fetch_encoded_device(sccg_reader* reader, const sccg_region* regions /*host*/, size_t n,
                                      const uint8_t* strand, const sccg_fetch_format* fmt, void* d_out,
                                      size_t out_cap /*bytes*/, size_t* out_len /*bytes*/, void* stream);
+
+/* Shared reference: R' -- the stripped, uppercased reference every token of a record indexes -- held
+ * once for all the readers opened over it.  A private reader (sccg_reader_open) keeps a copy of its
+ * own, by far the largest thing it holds; a hundred samples over one reference would hold a hundred.
+ *
+ * A record's N line decides which R' its tokens index: with an N-run line the reference's 'N' are
+ * erased before uppercasing (decompression.cpp:105-110; a lowercase 'n' stays, as "N"), with the N
+ * line "," -- a pair that stayed in local mode -- they are kept.  Neither form can be derived from
+ * the other on the device, so a reference holds the forms asked for (`forms`: SCCG_REF_ERASED,
+ * SCCG_REF_KEPT or both; 0 = both), each made by the very strip sccg_reader_open runs and kept in a
+ * device allocation of the reference's own.  sccg_reference_device_bytes is their sum (0 for NULL).
+ *
+ * sccg_reader_open_shared does everything sccg_reader_open does except the strip and the copy of R':
+ * it returns exactly the status sccg_reader_open returns for the same reference and record
+ * (SCCG_E_FORMAT, _PARSE, _RANGE, in that order), and SCCG_E_UNSUPPORTED, with sccg_last_error naming
+ * the form, for a record that needs a form the reference was opened without (known once the record's
+ * lines are, so after SCCG_E_FORMAT).  On any error *out is NULL.  Every reader call works on a
+ * shared reader and returns byte for byte what it returns on a private one.  The reader lives on the
+ * reference's context and shares its non-reentrancy.
+ *
+ * A reference is counted by its readers: sccg_reference_close drops the caller's hold (no further
+ * open through it), and the memory goes with the last reader's sccg_reader_close.  All of that
+ * happens before sccg_ctx_destroy.  sccg_reader_device_bytes is the reader's own persistent
+ * allocation (for a private reader R' included; the staging a fetch grows is not counted); 0 for NULL.
+ * The _device forms take device pointers and a hipStream_t (NULL = the context's own stream). */
+typedef struct sccg_reference sccg_reference;
+#define SCCG_REF_ERASED 1u   /* R' as a record with an N-run line needs it (N erased, decompression.cpp:105-110) */
+#define SCCG_REF_KEPT   2u   /* R' as a record whose N line is "," needs it (N kept) */
+int sccg_reference_open(sccg_ctx* ctx, const char* ref_fa, size_t ref_len, uint32_t forms /*0 = both*/, sccg_reference** out);
+int sccg_reference_open_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_len, uint32_t forms, sccg_reference** out,
+                               void* stream);
+void sccg_reference_close(sccg_reference* ref);             /* NULL: no-op */
+size_t sccg_reference_device_bytes(const sccg_reference* ref);
+int sccg_reader_open_shared(sccg_reference* ref, const char* rec_text, size_t rec_len, sccg_reader** out);
+int sccg_reader_open_shared_device(sccg_reference* ref, const void* d_rec, size_t rec_len, sccg_reader** out, void* stream);
+size_t sccg_reader_device_bytes(const sccg_reader* reader);
+
+/* Cohort: the encoded fetch over many readers at once, each region naming its sample -- a batch of
+ * windows drawn from many individuals costs one copy of the region list, one kernel launch and one
+ * synchronise, whatever n and the number of samples touched are.
+ *
+ * sccg_cohort_create takes n_samples readers, private or shared in any mix; a reader may appear
+ * twice.  All of them are on one context: anything else, n_samples == 0 or a NULL entry is
+ * SCCG_E_INVALID (*out NULL).  The cohort does NOT own its readers: it keeps a device table of what
+ * each reads, written once at create, so close the cohort BEFORE any of its readers, and every cohort
+ * before sccg_ctx_destroy.  It owns that table and region staging of its own, so sccg_compress /
+ * sccg_reconstruct and the readers' own fetches on the context do not disturb it; it shares the
+ * context's non-reentrancy.  sccg_cohort_close(NULL) is a no-op; sccg_cohort_samples(NULL) is 0.
+ *
+ * sccg_cohort_fetch / _device: region i is [begin, end) of sample `sample`, 0-based and half-open in
+ * that sample's sequence positions, on the reverse strand when bit 0 of `flags` is set or when the
+ * format carries SCCG_FETCH_REVCOMP (all regions; with both it is still reversed).  Output layout,
+ * encodings, dtypes, format flags, the size query (d_out == NULL), SCCG_E_NOMEM with *out_len = the
+ * bytes needed, and the alignment rule are exactly sccg_reader_fetch_encoded[_device]'s: region i
+ * takes bytes_per_base * (end - begin) bytes at the running offset, no separators; regions may be
+ * empty, repeat, overlap and come in any order of positions and samples; n == 0 gives an empty output.
+ *
+ * SCCG_E_INVALID, nothing written, sccg_last_error naming the first offender: every format error of
+ * the encoded fetch, a region with a flag bit other than bit 0, a sample outside [0, n_samples), or a
+ * region outside its own sample's 0 <= begin <= end <= length.  Both forms synchronise before
+ * returning; stream is a hipStream_t (NULL = the context's own). */
+typedef struct sccg_cohort sccg_cohort;
+typedef struct { int64_t begin, end; int32_t sample; uint32_t flags; } sccg_cohort_region;  /* flags bit 0: reverse strand; others 0 */
+int sccg_cohort_create(sccg_reader* const* readers, size_t n_samples, sccg_cohort** out);
+void sccg_cohort_close(sccg_cohort* cohort);                 /* NULL: no-op */
+size_t sccg_cohort_samples(const sccg_cohort* cohort);
+int sccg_cohort_fetch(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt, sccg_buf* out);
+int sccg_cohort_fetch_device(sccg_cohort* cohort, const sccg_cohort_region* regions /*host*/, size_t n,
+                             const sccg_fetch_format* fmt, void* d_out, size_t out_cap /*bytes*/, size_t* out_len /*bytes*/,
+                             void* stream);
 
 void sccg_buf_free(sccg_buf* b);
 

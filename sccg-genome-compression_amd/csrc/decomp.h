@@ -81,3 +81,14 @@ int dc_fetch(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, 
 // element size.  One launch, under the same profiler family as dc_fetch.
 int dc_fetch_encoded(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, int enc, int dt,
                      bool upper, bool all_rev, uint8_t* d_out, hipStream_t s);
+
+// A cohort's device table (sccg_cohort_create): one entry per sample, the reader's source and what
+// k_fetch_enc hoists per launch (nn = S.nr.n, nlr = S.lr.n, ntot = the N bases of the sequence).
+struct DcCohortEntry {
+    DcFetchSrc S;
+    int64_t nn, nlr, ntot;
+};
+// dc_fetch_encoded with the source chosen per region: region i reads d_tab[d_samp[i]] (every index
+// validated by the caller, as the regions are).  One launch, under the same profiler family.
+int dc_fetch_cohort(const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg, const int32_t* d_samp, int64_t nreg,
+                    int64_t F, int enc, int dt, bool upper, bool all_rev, uint8_t* d_out, hipStream_t s);

@@ -1170,101 +1170,59 @@ __device__ __forceinline__ uint32_t base_code(uint32_t c) {
     return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 4u;
 }
 
-struct FetchEncArgs {
-    DcFetchSrc S;
-    const int64_t* pre;   // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
-    const int64_t* beg;   // nreg: region begins, bit 63 set = reverse strand
-    int64_t nreg, F, o_first, nlr;   // o_first: the flat base of block 0's first base (<= 0)
-    uint32_t all_rev, elemwise;
-    uint8_t* out;
-};
+// A lane's bases of one span, shared by the encoded fetch kernels: positions j, j + 1, ... (ascending)
+// through the N runs from rn and the lowercase runs from rl, each final byte or code at its output
+// place mine[k0, k1) -- descending for a reversed span.
+template <int ENC>
+__device__ __forceinline__ void fetch_enc_walk(const int32_t* ns, const int32_t* nl,
+                                               const int64_t* ncum, const int32_t* ls,
+                                               const int32_t* ll, int64_t nn, int64_t nlr, int64_t ntot,
+                                               const uint8_t* sdec, uint8_t* mine, int64_t j, int64_t rn, int64_t rl, int64_t d0,
+                                               bool rev, int k0, int k1) {
+    int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot, l_s = INT64_MAX, l_e = INT64_MAX;
+    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+    if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
+    for (int t = 0; t < k1 - k0; t++) {
+        while (j >= n_e) {
+            rn++;
+            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+            else { n_s = n_e = INT64_MAX; n_b = ntot; }
+        }
+        while (j >= l_e) {
+            rl++;
+            if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
+            else l_s = l_e = INT64_MAX;
+        }
+        uint32_t c = j >= n_s ? (uint32_t)'N' : (uint32_t)sdec[j - n_b - d0];
+        if (ENC == FE_ASCII) {
+            if (j >= l_s) c = c_tolower((uint8_t)c);
+            if (rev) c = comp_ascii(c);
+        } else {
+            c = base_code(c);
+            if (rev && c < 4u) c = 3u - c;
+        }
+        j++;
+        mine[rev ? k1 - 1 - t : k0 + t] = (uint8_t)c;
+    }
+}
 
+// The streamed epilogue, shared likewise: the wave's finished tile fw (one byte per base, flat bases
+// [base, base + FT_W), of which [w0, fend) are this launch's) out in 16-byte pieces, piece q to lane
+// q % 64; cut pieces, and every piece when elemwise, element by element.
 template <int ENC, int DT>
-__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_enc(const FetchEncArgs A) {
+__device__ __forceinline__ void fetch_enc_stream(const uint8_t* fw, int64_t base, int64_t w0, int64_t fend, uint32_t elemwise,
+                                                 uint8_t* out, int lane) {
     constexpr int ES = DT == FD_U8 ? 1 : DT == FD_F32 ? 4 : 2;   // element bytes
     constexpr int BPB = ENC == FE_ONEHOT ? 4 * ES : 1;           // bytes per base
     constexpr int PB = 16 / BPB;                                 // bases per 16-byte piece
     constexpr uint32_t ONE = DT == FD_U8 ? 1u : DT == FD_F16 ? 0x3C00u : DT == FD_BF16 ? 0x3F80u : 0x3F800000u;
-    static_assert(ENC == FE_ONEHOT || DT == FD_U8, "ASCII and INDEX are bytes");
-    __shared__ uint8_t tile[WPB][FT_W];
-    __shared__ __attribute__((aligned(16))) uint8_t fin[WPB][FT_W];
-    __shared__ uint8_t stg[WPB][2 * TK_B];
-    const int lane = lane_id();
-    uint8_t* sdec = tile[wave_in_block()];
-    uint8_t* fw = fin[wave_in_block()];
-    uint8_t* st = stg[wave_in_block()];
-    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
-    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
-    const int64_t w0 = base < 0 ? 0 : base;
-    int64_t f = w0;
-    if (f >= fend) return;
-    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
-    const int32_t* __restrict__ ns = A.S.nr.start;
-    const int32_t* __restrict__ nl = A.S.nr.len;
-    const int64_t* __restrict__ ncum = A.S.nr.cum;
-    const int32_t* __restrict__ ls = A.S.lr.start;
-    const int32_t* __restrict__ ll = A.S.lr.len;
-    const int64_t nn = A.S.nr.n, nlr = ENC == FE_ASCII ? A.nlr : 0;
-    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
-    const int64_t* __restrict__ pre = A.pre;
-    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-    while (f < fend) {
-        if (pre[i + 1] <= f) {
-            i++;
-            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-        }
-        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
-        const int64_t braw = A.beg[i];
-        const bool rev = A.all_rev || braw < 0;
-        const int64_t bg = braw & INT64_MAX;
-        // reversed: flat base g of the region is position end - 1 - (g - pre[i]); [f, fe) covers [j0, j1)
-        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
-        const FetchSpan sp = fetch_decode_span(A.S, j0, j1, sdec, st);
-        const int64_t rn0 = sp.rn0, d0 = sp.d0;
-        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
-        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
-        if (ga < gb) {
-            // ascending in j; a reversed span's results land at descending places
-            int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f), rn = rn0, rl = rl0;
-            int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot, l_s = INT64_MAX, l_e = INT64_MAX;
-            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
-            if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
-            const int k0 = (int)(ga - g0), k1 = (int)(gb - g0);
-            uint8_t* mine = fw + lane * OPT;
-            for (int t = 0; t < k1 - k0; t++) {
-                while (j >= n_e) {
-                    rn++;
-                    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
-                    else { n_s = n_e = INT64_MAX; n_b = ntot; }
-                }
-                while (j >= l_e) {
-                    rl++;
-                    if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
-                    else l_s = l_e = INT64_MAX;
-                }
-                uint32_t c = j >= n_s ? (uint32_t)'N' : (uint32_t)sdec[j - n_b - d0];
-                if (ENC == FE_ASCII) {
-                    if (j >= l_s) c = c_tolower((uint8_t)c);
-                    if (rev) c = comp_ascii(c);
-                } else {
-                    c = base_code(c);
-                    if (rev && c < 4u) c = 3u - c;
-                }
-                j++;
-                mine[rev ? k1 - 1 - t : k0 + t] = (uint8_t)c;
-            }
-        }
-        wave_sync();   // (the tile is read before the next span fills it)
-        f = fe;
-    }
-    wave_sync();   // fin[w0 - base, fend - base) is complete
     for (int it = 0; it < BPB; it++) {
         const int q = it * 64 + lane;
         const int64_t p0 = base + (int64_t)q * PB;   // the piece's first base
         if (p0 >= fend || p0 + PB <= w0) continue;
         const uint8_t* src = fw + q * PB;
-        uint8_t* dst = A.out + p0 * BPB;
-        const bool full = !A.elemwise && p0 >= w0 && p0 + PB <= fend;
+        uint8_t* dst = out + p0 * BPB;
+        const bool full = !elemwise && p0 >= w0 && p0 + PB <= fend;
         if (BPB == 1) {
             if (full) {
                 *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
@@ -1306,6 +1264,160 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_enc(const FetchEncArgs A) 
             }
         }
     }
+}
+
+struct FetchEncArgs {
+    DcFetchSrc S;
+    const int64_t* pre;   // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
+    const int64_t* beg;   // nreg: region begins, bit 63 set = reverse strand
+    int64_t nreg, F, o_first, nlr;   // o_first: the flat base of block 0's first base (<= 0)
+    uint32_t all_rev, elemwise;
+    uint8_t* out;
+};
+
+template <int ENC, int DT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_enc(const FetchEncArgs A) {
+    static_assert(ENC == FE_ONEHOT || DT == FD_U8, "ASCII and INDEX are bytes");
+    __shared__ uint8_t tile[WPB][FT_W];
+    __shared__ __attribute__((aligned(16))) uint8_t fin[WPB][FT_W];
+    __shared__ uint8_t stg[WPB][2 * TK_B];
+    const int lane = lane_id();
+    uint8_t* sdec = tile[wave_in_block()];
+    uint8_t* fw = fin[wave_in_block()];
+    uint8_t* st = stg[wave_in_block()];
+    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
+    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
+    const int64_t w0 = base < 0 ? 0 : base;
+    int64_t f = w0;
+    if (f >= fend) return;
+    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
+    const int32_t* __restrict__ ns = A.S.nr.start;
+    const int32_t* __restrict__ nl = A.S.nr.len;
+    const int64_t* __restrict__ ncum = A.S.nr.cum;
+    const int32_t* __restrict__ ls = A.S.lr.start;
+    const int32_t* __restrict__ ll = A.S.lr.len;
+    const int64_t nn = A.S.nr.n, nlr = ENC == FE_ASCII ? A.nlr : 0;
+    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
+    const int64_t* __restrict__ pre = A.pre;
+    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+    while (f < fend) {
+        if (pre[i + 1] <= f) {
+            i++;
+            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+        }
+        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
+        const int64_t braw = A.beg[i];
+        const bool rev = A.all_rev || braw < 0;
+        const int64_t bg = braw & INT64_MAX;
+        // reversed: flat base g of the region is position end - 1 - (g - pre[i]); [f, fe) covers [j0, j1)
+        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
+        const FetchSpan sp = fetch_decode_span(A.S, j0, j1, sdec, st);
+        const int64_t rn0 = sp.rn0, d0 = sp.d0;
+        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
+        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
+        if (ga < gb) {
+            // ascending in j; a reversed span's results land at descending places
+            const int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f);
+            fetch_enc_walk<ENC>(ns, nl, ncum, ls, ll, nn, nlr, ntot, sdec, fw + lane * OPT, j, rn0, rl0, d0, rev, (int)(ga - g0),
+                                (int)(gb - g0));
+        }
+        wave_sync();   // (the tile is read before the next span fills it)
+        f = fe;
+    }
+    wave_sync();   // fin[w0 - base, fend - base) is complete
+    fetch_enc_stream<ENC, DT>(fw, base, w0, fend, A.elemwise, A.out, lane);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cohort fetch (sccg_cohort_fetch): k_fetch_enc with the source chosen per SPAN, not per launch.
+// Region i names its sample in samp[i]; the wave makes the index provably uniform (readfirstlane)
+// and reads that sample's entry of the cohort's table through a uniform address, so the entry
+// arrives by scalar loads and lives in SGPRs as k_fetch_enc's kernel arguments do.  The entry is
+// kept while consecutive spans stay on one sample.  What k_fetch_enc hoists per launch (the run
+// lists' pointers and counts, ntot) is per-span state here, taken from the entry.
+// ---------------------------------------------------------------------------------------------
+struct FetchCohortArgs {
+    const DcCohortEntry* tab;   // one entry per sample
+    const int64_t* pre;         // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
+    const int64_t* beg;         // nreg: region begins, bit 63 set = reverse strand
+    const int32_t* samp;        // nreg: region samples
+    int64_t nreg, F, o_first;
+    uint32_t all_rev, elemwise, upper;
+    uint8_t* out;
+};
+
+// A table entry through a wave-uniform index, read as constant memory (nothing writes the table
+// after sccg_cohort_create): with both, the loads are scalar and the entry lands in SGPRs.
+typedef const int64_t __attribute__((address_space(4))) * ConstWords;
+__device__ __forceinline__ DcCohortEntry cohort_entry(const DcCohortEntry* tab, int sm) {
+    constexpr int NW = (int)(sizeof(DcCohortEntry) / sizeof(int64_t));
+    static_assert(sizeof(DcCohortEntry) == NW * sizeof(int64_t), "an entry is whole 8-byte words");
+    const ConstWords w = (ConstWords)(uintptr_t)(tab + sm);
+    int64_t v[NW];
+#pragma unroll
+    for (int k = 0; k < NW; k++) v[k] = w[k];
+    DcCohortEntry E;
+    __builtin_memcpy(&E, v, sizeof E);
+    return E;
+}
+
+template <int ENC, int DT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_cohort(const FetchCohortArgs A) {
+    static_assert(ENC == FE_ONEHOT || DT == FD_U8, "ASCII and INDEX are bytes");
+    __shared__ uint8_t tile[WPB][FT_W];
+    __shared__ __attribute__((aligned(16))) uint8_t fin[WPB][FT_W];
+    __shared__ uint8_t stg[WPB][2 * TK_B];
+    const int lane = lane_id();
+    uint8_t* sdec = tile[wave_in_block()];
+    uint8_t* fw = fin[wave_in_block()];
+    uint8_t* st = stg[wave_in_block()];
+    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
+    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
+    const int64_t w0 = base < 0 ? 0 : base;
+    int64_t f = w0;
+    if (f >= fend) return;
+    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
+    const DcCohortEntry* __restrict__ tab = A.tab;
+    const int64_t* __restrict__ pre = A.pre;
+    const int32_t* __restrict__ samp = A.samp;
+    DcCohortEntry E{};   // the current span's sample
+    int cur = -1;
+    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+    while (f < fend) {
+        if (pre[i + 1] <= f) {
+            i++;
+            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+        }
+        const int sm = __builtin_amdgcn_readfirstlane(samp[i]);
+        if (sm != cur) {   // (wave-uniform: a scalar branch around scalar loads)
+            cur = sm;
+            E = cohort_entry(tab, sm);
+        }
+        const int32_t* __restrict__ ns = E.S.nr.start;
+        const int32_t* __restrict__ nl = E.S.nr.len;
+        const int64_t* __restrict__ ncum = E.S.nr.cum;
+        const int32_t* __restrict__ ls = E.S.lr.start;
+        const int32_t* __restrict__ ll = E.S.lr.len;
+        const int64_t nn = E.nn, nlr = ENC == FE_ASCII && !A.upper ? E.nlr : 0, ntot = E.ntot;
+        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
+        const int64_t braw = A.beg[i];
+        const bool rev = A.all_rev || braw < 0;
+        const int64_t bg = braw & INT64_MAX;
+        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
+        const FetchSpan sp = fetch_decode_span(E.S, j0, j1, sdec, st);
+        const int64_t rn0 = sp.rn0, d0 = sp.d0;
+        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
+        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
+        if (ga < gb) {
+            const int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f);
+            fetch_enc_walk<ENC>(ns, nl, ncum, ls, ll, nn, nlr, ntot, sdec, fw + lane * OPT, j, rn0, rl0, d0, rev, (int)(ga - g0),
+                                (int)(gb - g0));
+        }
+        wave_sync();   // (the tile is read before the next span fills it)
+        f = fe;
+    }
+    wave_sync();   // fin[w0 - base, fend - base) is complete
+    fetch_enc_stream<ENC, DT>(fw, base, w0, fend, A.elemwise, A.out, lane);
 }
 
 }  // namespace
@@ -1527,6 +1639,28 @@ int dc_fetch_encoded(const DcFetchSrc& src, const int64_t* d_pre, const int64_t*
     else if (enc == FE_ONEHOT && dt == FD_F32) SCCG_FETCH_ENC(FE_ONEHOT, FD_F32);
     else return SCCG_E_INVALID;
 #undef SCCG_FETCH_ENC
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
+int dc_fetch_cohort(const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg, const int32_t* d_samp, int64_t nreg,
+                    int64_t F, int enc, int dt, bool upper, bool all_rev, uint8_t* d_out, hipStream_t s) {
+    if (F <= 0) return 0;
+    const int es = dt == FD_U8 ? 1 : dt == FD_F32 ? 4 : 2, bpb = enc == FE_ONEHOT ? 4 * es : 1;
+    const bool elemwise = ((uintptr_t)d_out % (uintptr_t)bpb) != 0;   // (as dc_fetch_encoded)
+    FetchCohortArgs A{d_tab, d_pre, d_beg, d_samp, nreg, F, elemwise ? 0 : -(int64_t)(((uintptr_t)d_out & 15) / (uintptr_t)bpb),
+                      all_rev ? 1u : 0u, elemwise ? 1u : 0u, upper ? 1u : 0u, d_out};
+    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
+#define SCCG_FETCH_COHORT(E, D) \
+    PROF_LAUNCH(PROF_FETCH, s, (k_fetch_cohort<E, D>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A)
+    if (enc == FE_ASCII && dt == FD_U8) SCCG_FETCH_COHORT(FE_ASCII, FD_U8);
+    else if (enc == FE_INDEX && dt == FD_U8) SCCG_FETCH_COHORT(FE_INDEX, FD_U8);
+    else if (enc == FE_ONEHOT && dt == FD_U8) SCCG_FETCH_COHORT(FE_ONEHOT, FD_U8);
+    else if (enc == FE_ONEHOT && dt == FD_F16) SCCG_FETCH_COHORT(FE_ONEHOT, FD_F16);
+    else if (enc == FE_ONEHOT && dt == FD_BF16) SCCG_FETCH_COHORT(FE_ONEHOT, FD_BF16);
+    else if (enc == FE_ONEHOT && dt == FD_F32) SCCG_FETCH_COHORT(FE_ONEHOT, FD_F32);
+    else return SCCG_E_INVALID;
+#undef SCCG_FETCH_COHORT
     SCCG_HIP(hipGetLastError());
     return 0;
 }

@@ -215,11 +215,27 @@ struct sccg_ctx {
     }
 };
 
+// A shared reference (sccg_reference_open): R' in the forms asked for, each in a device allocation of
+// its own (DPAD readable bytes behind it, then the form's length as one int64: what a shared open
+// copies into the slot the strip fills).  Counted by the caller's hold and by its readers.
+constexpr int REF_ERASED = 0, REF_KEPT = 1;   // FILTER_DROP_UPPERN_ONLY, FILTER_UPPER
+struct sccg_reference {
+    sccg_ctx* ctx = nullptr;
+    void* mem[2] = {nullptr, nullptr};
+    size_t bytes[2] = {0, 0};   // of each allocation; 0: the form is not held
+    int64_t holds = 1;          // the caller's (until sccg_reference_close) + one per reader
+    const int64_t* d_len(int form) const {
+        return reinterpret_cast<const int64_t*>(reinterpret_cast<const uint8_t*>(mem[form]) + bytes[form] - 256);
+    }
+};
+
 // A region reader (sccg_reader_open): what a fetch reads, in device memory of its own -- never a
 // pooled slot of the context, which the next compress / reconstruct reuses.
 struct sccg_reader {
     sccg_ctx* ctx = nullptr;
-    void* mem = nullptr;        // R', the record line, its block index, both run lists (src points into it)
+    sccg_reference* ref = nullptr;   // a shared open: src.R points into it, and the reader holds it
+    size_t mem_bytes = 0;
+    void* mem = nullptr;        // R' (a private open), the record line, its block index, both run lists (src points into it)
     DcFetchSrc src{};
     int64_t length = 0;         // bases in the sequence (reconstruct_impl's nres)
     std::string header;         // the header line, '>' included, no '\n'; empty: none
@@ -227,6 +243,19 @@ struct sccg_reader {
     int64_t* h_reg = nullptr;
     size_t reg_cap = 0;
     void* d_out = nullptr;      // sccg_reader_fetch's device output
+    size_t out_cap = 0;
+};
+
+// A cohort (sccg_cohort_create): the device table of its readers' sources, and region staging and a
+// host-call output buffer of its own.  The readers stay the caller's.
+struct sccg_cohort {
+    sccg_ctx* ctx = nullptr;
+    std::vector<int64_t> length;   // per sample
+    void* d_tab = nullptr;         // DcCohortEntry per sample
+    void* d_reg = nullptr;         // a fetch's region list: device copy and its pinned host image
+    int64_t* h_reg = nullptr;
+    size_t reg_cap = 0;
+    void* d_out = nullptr;         // sccg_cohort_fetch's device output
     size_t out_cap = 0;
 };
 
@@ -1334,11 +1363,15 @@ int reader_alloc_fail(sccg_ctx* ctx, hipError_t e, size_t bytes) {
     return ctx->fail(e == hipErrorOutOfMemory ? SCCG_E_NOMEM : SCCG_E_HIP, "reader allocation of %zu bytes failed", bytes);
 }
 
+void reference_drop(sccg_reference* ref);
+
 // The front half of reconstruct_impl on the one stream -- lines, reference strip, run lines, the
 // record line's block index, every check (same statuses, same order as the size query) -- then
 // copies of what a fetch reads into one allocation of the reader's own: the context's slots are
 // reused by the next call.
-int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_t* rec, int64_t n, sccg_reader* rd) {
+// (ref given: a shared open -- no strip and no copy of R'; rfa / rn are not looked at)
+int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_t* rec, int64_t n, sccg_reader* rd,
+                     sccg_reference* ref = nullptr) {
     hipStream_t s = ctx->stream;
     GET(int64_t, sc, B_SCAL, 64);
     RecLines L;
@@ -1351,9 +1384,21 @@ int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     const int64_t nlower = L.nlower, nnl = L.nnl, nenc = L.nenc;
     const bool n_is_comma = L.n_is_comma;
     // reference (decompression.cpp:47-58, 105-110): the N line "," keeps its N's (FILTER_UPPER)
-    GET(uint8_t, Rp, B_RP, rn + 64);
-    TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, nullptr, sc + 8, nullptr, nullptr,
-              n_is_comma ? FILTER_UPPER : FILTER_DROP_UPPERN_ONLY, Rp, 1, s));
+    const int form = n_is_comma ? REF_KEPT : REF_ERASED;
+    const uint8_t* Rp = nullptr;
+    if (ref) {
+        if (!ref->mem[form])
+            return ctx->fail(SCCG_E_UNSUPPORTED, "the record needs the reference's %s form (%s), which it was opened without",
+                             form == REF_KEPT ? "kept" : "erased", form == REF_KEPT ? "SCCG_REF_KEPT" : "SCCG_REF_ERASED");
+        // |R'| where the strip leaves it: the token range check reads it there
+        HIPTRY(hipMemcpyAsync(sc + 9, ref->d_len(form), sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        Rp = reinterpret_cast<const uint8_t*>(ref->mem[form]);
+    } else {
+        GET(uint8_t, Rp1, B_RP, rn + 64);
+        TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, nullptr, sc + 8, nullptr, nullptr,
+                  n_is_comma ? FILTER_UPPER : FILTER_DROP_UPPERN_ONLY, Rp1, 1, s));
+        Rp = Rp1;
+    }
     GET(int64_t, lp2, B_D_LP2, nenc + 1);
     GET(int64_t, dlt2, B_D_DLT2, nenc + 1);
     GET(int64_t, part2, B_PARTIAL2, scan_partials_needed(nenc + 1) + 16);
@@ -1404,18 +1449,19 @@ int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
         off += (bytes + 255) & ~(size_t)255;
         return at;
     };
-    const size_t o_R = part_at((size_t)nRp + DPAD), o_rec = part_at((size_t)nenc + DPAD);
+    const size_t o_R = ref ? 0 : part_at((size_t)nRp + DPAD), o_rec = part_at((size_t)nenc + DPAD);
     const size_t o_bin = part_at((size_t)nblk * 8), o_boff = part_at((size_t)nblk * 8), o_bdsum = part_at((size_t)nblk * 8);
     const size_t o_ns = part_at((size_t)nr.n * 4), o_nl = part_at((size_t)nr.n * 4), o_nc = part_at((size_t)nr.n * 8);
     const size_t o_ls = part_at((size_t)lr.n * 4), o_ll = part_at((size_t)lr.n * 4);
     const size_t bytes = off + 256;
     const hipError_t e = hipMalloc(&rd->mem, bytes);
     if (e != hipSuccess) { rd->mem = nullptr; return reader_alloc_fail(ctx, e, bytes); }
+    rd->mem_bytes = bytes;
     uint8_t* m = reinterpret_cast<uint8_t*>(rd->mem);
     auto keep = [&](size_t at, const void* src, size_t nbytes) {
         return nbytes ? hipMemcpyAsync(m + at, src, nbytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
     };
-    HIPTRY(keep(o_R, Rp, (size_t)nRp));
+    if (!ref) HIPTRY(keep(o_R, Rp, (size_t)nRp));
     HIPTRY(keep(o_rec, enc, (size_t)nenc));
     HIPTRY(keep(o_bin, lp2, (size_t)nblk * 8));
     HIPTRY(keep(o_boff, doff, (size_t)nblk * 8));
@@ -1436,7 +1482,11 @@ int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     S.bin = reinterpret_cast<const int64_t*>(m + o_bin);
     S.boff = reinterpret_cast<const int64_t*>(m + o_boff);
     S.bdsum = reinterpret_cast<const int64_t*>(m + o_bdsum);
-    S.R = m + o_R;
+    S.R = ref ? Rp : m + o_R;
+    if (ref) {
+        rd->ref = ref;
+        ref->holds++;
+    }
     S.nr = DcRuns{reinterpret_cast<int32_t*>(m + o_ns), reinterpret_cast<int32_t*>(m + o_nl),
                   reinterpret_cast<int64_t*>(m + o_nc), nr.n, nr.total};
     S.lr = DcRuns{reinterpret_cast<int32_t*>(m + o_ls), reinterpret_cast<int32_t*>(m + o_ll), nullptr, lr.n, lr.total};
@@ -1451,13 +1501,15 @@ void reader_free(sccg_reader* rd) {
     if (rd->d_reg) (void)hipFree(rd->d_reg);
     if (rd->h_reg) (void)hipHostFree(rd->h_reg);
     if (rd->d_out) (void)hipFree(rd->d_out);
+    if (rd->ref) reference_drop(rd->ref);
     delete rd;
 }
 
-int reader_open(sccg_ctx* ctx, const uint8_t* d_rfa, int64_t rn, const uint8_t* d_rec, int64_t n, sccg_reader** out) {
+int reader_open(sccg_ctx* ctx, const uint8_t* d_rfa, int64_t rn, const uint8_t* d_rec, int64_t n, sccg_reader** out,
+                sccg_reference* ref = nullptr) {
     sccg_reader* rd = new sccg_reader();
     rd->ctx = ctx;
-    const int rc = reader_open_impl(ctx, d_rfa, rn, d_rec, n, rd);
+    const int rc = reader_open_impl(ctx, d_rfa, rn, d_rec, n, rd, ref);
     if (rc) {
         (void)hipStreamSynchronize(ctx->stream);   // (nothing of the failed open is still queued)
         reader_free(rd);
@@ -1526,6 +1578,129 @@ int fetch_run(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t F, 
                              (flags & SCCG_FETCH_UPPER) != 0, (flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
     else
         TRY(dc_fetch(rd->src, d, d + n + 1, (int64_t)n, F, (flags & SCCG_FETCH_UPPER) != 0, d_out, s));
+    HIPTRY(hipStreamSynchronize(s));
+    return SCCG_OK;
+}
+
+// -------------------------------------------------------------------------------------------
+// shared reference (sccg_reference_*) and cohort (sccg_cohort_*)
+// -------------------------------------------------------------------------------------------
+// one hold less; the memory goes with the last
+void reference_drop(sccg_reference* ref) {
+    if (--ref->holds > 0) return;
+    (void)hipSetDevice(ref->ctx->device);
+    for (int f = 0; f < 2; f++)
+        if (ref->mem[f]) (void)hipFree(ref->mem[f]);
+    delete ref;
+}
+
+// each form asked for by the strip call reader_open_impl makes for it, into an allocation of its own
+int reference_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, uint32_t forms, sccg_reference* ref) {
+    hipStream_t s = ctx->stream;
+    GET(int64_t, sc, B_SCAL, 64);
+    GET(uint8_t, Rp, B_RP, rn + 64);
+    for (int f = 0; f < 2; f++) {
+        if (!(forms & (f == REF_KEPT ? SCCG_REF_KEPT : SCCG_REF_ERASED))) continue;
+        TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, nullptr, sc + 8, nullptr, nullptr,
+                  f == REF_KEPT ? FILTER_UPPER : FILTER_DROP_UPPERN_ONLY, Rp, 1, s));
+        int64_t nRp = 0;
+        const RbItem it{sc + 9, &nRp, (int)sizeof nRp};
+        TRY(dev_readback(&it, 1, s));
+        // R', DPAD of readable slack, and |R'| in the last 256-byte part
+        const size_t bytes = (((size_t)nRp + DPAD + 255) & ~(size_t)255) + 256;
+        const hipError_t e = hipMalloc(&ref->mem[f], bytes);
+        if (e != hipSuccess) { ref->mem[f] = nullptr; return reader_alloc_fail(ctx, e, bytes); }
+        ref->bytes[f] = bytes;
+        uint8_t* m = reinterpret_cast<uint8_t*>(ref->mem[f]);
+        if (nRp) HIPTRY(hipMemcpyAsync(m, Rp, (size_t)nRp, hipMemcpyDeviceToDevice, s));
+        HIPTRY(hipMemsetAsync(m + nRp, 0, bytes - (size_t)nRp, s));
+        HIPTRY(hipMemcpyAsync(m + bytes - 256, sc + 9, sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        HIPTRY(hipStreamSynchronize(s));   // (the next form's strip reuses Rp and the scalars)
+    }
+    return SCCG_OK;
+}
+
+int reference_open(sccg_ctx* ctx, const uint8_t* d_rfa, int64_t rn, uint32_t forms, sccg_reference** out) {
+    sccg_reference* ref = new sccg_reference();
+    ref->ctx = ctx;
+    const int rc = reference_open_impl(ctx, d_rfa, rn, forms, ref);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        reference_drop(ref);
+        return rc;
+    }
+    *out = ref;
+    return SCCG_OK;
+}
+
+void cohort_free(sccg_cohort* co) {
+    if (!co) return;
+    (void)hipSetDevice(co->ctx->device);
+    if (co->d_tab) (void)hipFree(co->d_tab);
+    if (co->d_reg) (void)hipFree(co->d_reg);
+    if (co->h_reg) (void)hipHostFree(co->h_reg);
+    if (co->d_out) (void)hipFree(co->d_out);
+    delete co;
+}
+
+// the format (as the encoded fetch's), then every region: its flags, its sample, its range in that
+// sample; SCCG_E_INVALID names the first offender.  *F: the regions' total length
+int cohort_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt, size_t* bpb, int64_t* F) {
+    sccg_ctx* ctx = co->ctx;
+    *bpb = fetch_format_bpb(fmt);
+    if (!*bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
+                                fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
+    if (!regions && n) return ctx->fail(SCCG_E_INVALID, "null region list");
+    const int64_t ns = (int64_t)co->length.size();
+    int64_t tot = 0;
+    for (size_t i = 0; i < n; i++) {
+        const sccg_cohort_region& r = regions[i];
+        if (r.flags & ~1u) return ctx->fail(SCCG_E_INVALID, "region %zu has unknown flag bits (flags %u)", i, r.flags);
+        if (r.sample < 0 || r.sample >= ns)
+            return ctx->fail(SCCG_E_INVALID, "region %zu names sample %d, outside [0, %lld)", i, (int)r.sample, (long long)ns);
+        const int64_t len = co->length[(size_t)r.sample];
+        if (r.begin < 0 || r.end < r.begin || r.end > len)
+            return ctx->fail(SCCG_E_INVALID, "region %zu [%lld, %lld) is outside sample %d's sequence [0, %lld)", i,
+                             (long long)r.begin, (long long)r.end, (int)r.sample, (long long)len);
+        tot += r.end - r.begin;
+    }
+    *F = tot;
+    return SCCG_OK;
+}
+
+// fetch_run for a cohort: one pinned image -- [0, n] the prefix of the lengths, (n, 2n] the begins
+// with the strand in bit 63, then the samples as int32 -- in one copy; one launch; one sync
+int cohort_run(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, int64_t F, const sccg_fetch_format* fmt,
+               uint8_t* d_out, hipStream_t s) {
+    sccg_ctx* ctx = co->ctx;
+    const size_t words = 2 * n + 1, bytes = words * sizeof(int64_t) + n * sizeof(int32_t);
+    if (co->reg_cap < bytes) {
+        const size_t cap = bytes + bytes / 2 + 4096;
+        if (co->d_reg) (void)hipFree(co->d_reg);
+        if (co->h_reg) (void)hipHostFree(co->h_reg);
+        co->d_reg = nullptr;
+        co->h_reg = nullptr;
+        co->reg_cap = 0;
+        hipError_t e = hipMalloc(&co->d_reg, cap);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&co->h_reg), cap, hipHostMallocDefault);
+        if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
+        co->reg_cap = cap;
+    }
+    int64_t* h = co->h_reg;
+    int32_t* hs = reinterpret_cast<int32_t*>(h + words);
+    int64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        h[i] = at;
+        h[n + 1 + i] = regions[i].begin | ((regions[i].flags & 1u) ? INT64_MIN : 0);
+        hs[i] = regions[i].sample;
+        at += regions[i].end - regions[i].begin;
+    }
+    h[n] = at;
+    int64_t* d = reinterpret_cast<int64_t*>(co->d_reg);
+    HIPTRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
+    TRY(dc_fetch_cohort(reinterpret_cast<const DcCohortEntry*>(co->d_tab), d, d + n + 1, reinterpret_cast<const int32_t*>(d + words),
+                        (int64_t)n, F, (int)fmt->encoding, (int)fmt->dtype, (fmt->flags & SCCG_FETCH_UPPER) != 0,
+                        (fmt->flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
     HIPTRY(hipStreamSynchronize(s));
     return SCCG_OK;
 }
@@ -1775,6 +1950,153 @@ int sccg_reader_fetch_encoded(sccg_reader* reader, const sccg_region* regions, s
         rc = fetch_run(reader, regions, n, F, fmt->flags, (uint8_t*)reader->d_out, ctx->stream, fmt, strand);
         if (rc) { free(h); return rc; }
         const hipError_t e = hipMemcpy(h, reader->d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { free(h); return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__)); }
+    }
+    h[bytes] = 0;
+    out->data = h;
+    out->len = bytes;
+    return SCCG_OK;
+}
+
+int sccg_reference_open_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_len, uint32_t forms, sccg_reference** out,
+                               void* stream) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (!d_ref_fa && ref_len)) return SCCG_E_INVALID;
+    if (forms & ~(SCCG_REF_ERASED | SCCG_REF_KEPT)) return ctx->fail(SCCG_E_INVALID, "unknown reference form bits (forms %u)", forms);
+    if (!forms) forms = SCCG_REF_ERASED | SCCG_REF_KEPT;
+    HIPTRY(hipSetDevice(ctx->device));
+    hipStream_t saved = ctx->stream;
+    if (stream) ctx->stream = (hipStream_t)stream;
+    const int rc = reference_open(ctx, (const uint8_t*)d_ref_fa, (int64_t)ref_len, forms, out);
+    ctx->stream = saved;
+    return rc;
+}
+
+int sccg_reference_open(sccg_ctx* ctx, const char* ref_fa, size_t ref_len, uint32_t forms, sccg_reference** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || (!ref_fa && ref_len)) return SCCG_E_INVALID;
+    HIPTRY(hipSetDevice(ctx->device));
+    uint8_t* drf = reinterpret_cast<uint8_t*>(ctx->get(B_RFA, ref_len + 16));
+    if (!drf) return ctx->fail(SCCG_E_NOMEM, "device allocation failed");
+    if (ref_len) HIPTRY(hipMemcpyAsync(drf, ref_fa, ref_len, hipMemcpyHostToDevice, ctx->stream));
+    return sccg_reference_open_device(ctx, drf, ref_len, forms, out, nullptr);
+}
+
+void sccg_reference_close(sccg_reference* ref) {
+    if (ref) reference_drop(ref);
+}
+
+size_t sccg_reference_device_bytes(const sccg_reference* ref) { return ref ? ref->bytes[0] + ref->bytes[1] : 0; }
+
+int sccg_reader_open_shared_device(sccg_reference* ref, const void* d_rec, size_t rec_len, sccg_reader** out, void* stream) {
+    if (out) *out = nullptr;
+    if (!ref || !out || (!d_rec && rec_len)) return SCCG_E_INVALID;
+    sccg_ctx* ctx = ref->ctx;
+    HIPTRY(hipSetDevice(ctx->device));
+    hipStream_t saved = ctx->stream;
+    if (stream) ctx->stream = (hipStream_t)stream;
+    const int rc = reader_open(ctx, nullptr, 0, (const uint8_t*)d_rec, (int64_t)rec_len, out, ref);
+    ctx->stream = saved;
+    return rc;
+}
+
+int sccg_reader_open_shared(sccg_reference* ref, const char* rec_text, size_t rec_len, sccg_reader** out) {
+    if (out) *out = nullptr;
+    if (!ref || !out || (!rec_text && rec_len)) return SCCG_E_INVALID;
+    sccg_ctx* ctx = ref->ctx;
+    HIPTRY(hipSetDevice(ctx->device));
+    uint8_t* drc = reinterpret_cast<uint8_t*>(ctx->get(B_TFA, rec_len + 16));
+    if (!drc) return ctx->fail(SCCG_E_NOMEM, "device allocation failed");
+    if (rec_len) HIPTRY(hipMemcpyAsync(drc, rec_text, rec_len, hipMemcpyHostToDevice, ctx->stream));
+    return reader_open(ctx, nullptr, 0, drc, (int64_t)rec_len, out, ref);
+}
+
+size_t sccg_reader_device_bytes(const sccg_reader* reader) { return reader ? reader->mem_bytes : 0; }
+
+int sccg_cohort_create(sccg_reader* const* readers, size_t n_samples, sccg_cohort** out) {
+    if (out) *out = nullptr;
+    if (!readers || !out || !n_samples || !readers[0]) return SCCG_E_INVALID;
+    sccg_ctx* ctx = readers[0]->ctx;
+    for (size_t i = 0; i < n_samples; i++) {
+        if (!readers[i]) return ctx->fail(SCCG_E_INVALID, "reader %zu is NULL", i);
+        if (readers[i]->ctx != ctx) return ctx->fail(SCCG_E_INVALID, "reader %zu is on another context than reader 0", i);
+    }
+    if (n_samples > (size_t)INT32_MAX) return ctx->fail(SCCG_E_INVALID, "a cohort holds at most 2^31 - 1 samples");
+    HIPTRY(hipSetDevice(ctx->device));
+    std::vector<DcCohortEntry> tab(n_samples);
+    sccg_cohort* co = new sccg_cohort();
+    co->ctx = ctx;
+    co->length.resize(n_samples);
+    for (size_t i = 0; i < n_samples; i++) {
+        const DcFetchSrc& S = readers[i]->src;
+        tab[i] = DcCohortEntry{S, S.nr.n, S.lr.n, S.nr.total};
+        co->length[i] = readers[i]->length;
+    }
+    const size_t bytes = n_samples * sizeof(DcCohortEntry);
+    hipError_t e = hipMalloc(&co->d_tab, bytes);
+    if (e != hipSuccess) {
+        co->d_tab = nullptr;
+        cohort_free(co);
+        return reader_alloc_fail(ctx, e, bytes);
+    }
+    e = hipMemcpy(co->d_tab, tab.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        cohort_free(co);
+        return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__));
+    }
+    *out = co;
+    return SCCG_OK;
+}
+
+void sccg_cohort_close(sccg_cohort* cohort) { cohort_free(cohort); }
+
+size_t sccg_cohort_samples(const sccg_cohort* cohort) { return cohort ? cohort->length.size() : 0; }
+
+int sccg_cohort_fetch_device(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt,
+                             void* d_out, size_t out_cap, size_t* out_len, void* stream) {
+    if (!cohort || !fmt || !out_len) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    size_t bpb = 0;
+    int64_t F = 0;
+    const size_t bpb0 = fetch_format_bpb(fmt);
+    if (bpb0) {
+        const size_t es = fmt->encoding == SCCG_ENC_ONEHOT ? bpb0 / 4 : 1;
+        if ((uintptr_t)d_out % es) return ctx->fail(SCCG_E_INVALID, "d_out is not aligned to the %zu-byte element", es);
+    }
+    const int rc = cohort_check(cohort, regions, n, fmt, &bpb, &F);
+    if (rc) return rc;
+    *out_len = (size_t)F * bpb;
+    if (!d_out) return SCCG_OK;   // size query
+    if ((size_t)F * bpb > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu bytes", (size_t)F * bpb);
+    if (F == 0) return SCCG_OK;
+    HIPTRY(hipSetDevice(ctx->device));
+    return cohort_run(cohort, regions, n, F, fmt, (uint8_t*)d_out, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sccg_cohort_fetch(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt, sccg_buf* out) {
+    if (!cohort || !fmt || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    size_t bpb = 0;
+    int64_t F = 0;
+    int rc = cohort_check(cohort, regions, n, fmt, &bpb, &F);
+    if (rc) return rc;   // (nothing written: *out is the caller's as it was)
+    const size_t bytes = (size_t)F * bpb;
+    char* h = (char*)malloc(bytes + 1);
+    if (!h) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
+    if (F > 0) {
+        HIPTRY(hipSetDevice(ctx->device));
+        if (cohort->out_cap < bytes + 16) {   // the cohort's own output buffer, grown on demand
+            if (cohort->d_out) (void)hipFree(cohort->d_out);
+            cohort->d_out = nullptr;
+            cohort->out_cap = 0;
+            const size_t cap = bytes + bytes / 4 + 4096;
+            const hipError_t e = hipMalloc(&cohort->d_out, cap);
+            if (e != hipSuccess) { free(h); cohort->d_out = nullptr; return reader_alloc_fail(ctx, e, cap); }
+            cohort->out_cap = cap;
+        }
+        rc = cohort_run(cohort, regions, n, F, fmt, (uint8_t*)cohort->d_out, ctx->stream);
+        if (rc) { free(h); return rc; }
+        const hipError_t e = hipMemcpy(h, cohort->d_out, bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) { free(h); return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__)); }
     }
     h[bytes] = 0;

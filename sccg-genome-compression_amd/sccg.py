@@ -21,6 +21,7 @@ SCCG_E_DELTA_STOI = 4
 OPT_EXACT_SWITCH = 1   # sccg_ctx_set_option (include/sccg.h)
 FETCH_UPPER = 1        # sccg_reader_fetch flags
 FETCH_REVCOMP = 2      # sccg_reader_fetch_encoded: every region on the reverse strand
+REF_FORMS = {"erased": 1, "kept": 2}                       # SCCG_REF_*: which R' a record's N line asks for
 ENCODINGS = {"ascii": 0, "index": 1, "onehot": 2}          # SCCG_ENC_*
 DTYPES = {"u8": 0, "f16": 1, "bf16": 2, "f32": 3}          # SCCG_DT_*
 ERRORS = {1: "SCCG_E_INVALID", 2: "SCCG_E_HIP", 3: "SCCG_E_NOMEM", 4: "SCCG_E_DELTA_STOI",
@@ -60,6 +61,11 @@ class Stats(ctypes.Structure):
 class Region(ctypes.Structure):
     """sccg_region: 0-based, half-open sequence positions."""
     _fields_ = [("begin", ctypes.c_int64), ("end", ctypes.c_int64)]
+
+
+class CohortRegion(ctypes.Structure):
+    """sccg_cohort_region: a region of one sample; flags bit 0 = reverse strand."""
+    _fields_ = [("begin", ctypes.c_int64), ("end", ctypes.c_int64), ("sample", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class FetchFormat(ctypes.Structure):
@@ -158,6 +164,25 @@ def load_library():
                                                   ctypes.POINTER(Buf)]
         lib.sccg_reader_fetch_encoded_device.argtypes = [vp, ctypes.POINTER(Region), sz, c, ctypes.POINTER(FetchFormat),
                                                          vp, sz, ctypes.POINTER(sz), vp]
+    if hasattr(lib, "sccg_reference_open"):   # (absent from builds older than the cohort fetch: A/B runs)
+        lib.sccg_reference_open.argtypes = [vp, c, sz, ctypes.c_uint32, ctypes.POINTER(vp)]
+        lib.sccg_reference_open_device.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.POINTER(vp), vp]
+        lib.sccg_reference_close.argtypes = [vp]
+        lib.sccg_reference_close.restype = None
+        lib.sccg_reference_device_bytes.argtypes = [vp]
+        lib.sccg_reference_device_bytes.restype = sz
+        lib.sccg_reader_open_shared.argtypes = [vp, c, sz, ctypes.POINTER(vp)]
+        lib.sccg_reader_open_shared_device.argtypes = [vp, vp, sz, ctypes.POINTER(vp), vp]
+        lib.sccg_reader_device_bytes.argtypes = [vp]
+        lib.sccg_reader_device_bytes.restype = sz
+        lib.sccg_cohort_create.argtypes = [ctypes.POINTER(vp), sz, ctypes.POINTER(vp)]
+        lib.sccg_cohort_close.argtypes = [vp]
+        lib.sccg_cohort_close.restype = None
+        lib.sccg_cohort_samples.argtypes = [vp]
+        lib.sccg_cohort_samples.restype = sz
+        lib.sccg_cohort_fetch.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, ctypes.POINTER(FetchFormat), ctypes.POINTER(Buf)]
+        lib.sccg_cohort_fetch_device.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, ctypes.POINTER(FetchFormat), vp, sz,
+                                                 ctypes.POINTER(sz), vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -311,6 +336,34 @@ class Context:
             self._err(rc)
         return Reader(self, ptr)
 
+    @staticmethod
+    def _forms(forms) -> int:
+        bad = [f for f in forms if f not in REF_FORMS]
+        if bad or not forms:
+            raise ValueError(f"forms {tuple(forms)!r}: a non-empty choice of {sorted(REF_FORMS)}")
+        mask = 0
+        for f in forms:
+            mask |= REF_FORMS[f]
+        return mask
+
+    def open_reference(self, ref_fa: bytes, forms=("erased", "kept")) -> "Reference":
+        """A shared reference (sccg_reference_open): R' held once for every reader opened through it.
+        forms: "erased" (records with an N-run line), "kept" (records whose N line is ","), or both."""
+        ptr = ctypes.c_void_p()
+        rc = self.lib.sccg_reference_open(self.ptr, ref_fa, len(ref_fa), self._forms(forms), ctypes.byref(ptr))
+        if rc:
+            self._err(rc)
+        return Reference(self, ptr)
+
+    def open_reference_device(self, d_ref: int, ref_len: int, forms=("erased", "kept"), stream: int = 0) -> "Reference":
+        """open_reference on a device-resident FASTA (sccg_reference_open_device)."""
+        ptr = ctypes.c_void_p()
+        rc = self.lib.sccg_reference_open_device(self.ptr, d_ref, ref_len, self._forms(forms), ctypes.byref(ptr),
+                                                 stream or None)
+        if rc:
+            self._err(rc)
+        return Reference(self, ptr)
+
     def profile(self, enable: bool = True, families: list | None = None) -> None:
         """Reset and enable (or disable) per-kernel HIP-event timing; `families` (names from
         sccg_profile_name) limits the bracketed launches to those families."""
@@ -385,6 +438,50 @@ class Context:
         return out
 
 
+class Reference:
+    """sccg_reference: R' shared by the readers opened through it.  close() drops this object's hold;
+    the device memory goes with the last of its readers."""
+
+    def __init__(self, ctx: Context, ptr: ctypes.c_void_p):
+        self.ctx, self.lib, self.ptr = ctx, ctx.lib, ptr
+
+    def close(self):
+        if self.ptr:
+            self.lib.sccg_reference_close(self.ptr)
+            self.ptr = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def device_bytes(self) -> int:
+        """Device bytes of the forms held (sccg_reference_device_bytes)."""
+        return self.lib.sccg_reference_device_bytes(self.ptr)
+
+    def open_reader(self, record: bytes) -> "Reader":
+        """Context.open_reader without the strip and without a private R' (sccg_reader_open_shared)."""
+        if not self.ptr:
+            raise ValueError("the reference is closed")
+        ptr = ctypes.c_void_p()
+        rc = self.lib.sccg_reader_open_shared(self.ptr, record, len(record), ctypes.byref(ptr))
+        if rc:
+            self.ctx._err(rc)
+        return Reader(self.ctx, ptr)
+
+    def open_reader_device(self, d_rec: int, rec_len: int, stream: int = 0) -> "Reader":
+        """open_reader on a device-resident record (sccg_reader_open_shared_device)."""
+        if not self.ptr:
+            raise ValueError("the reference is closed")
+        ptr = ctypes.c_void_p()
+        rc = self.lib.sccg_reader_open_shared_device(self.ptr, d_rec, rec_len, ctypes.byref(ptr), stream or None)
+        if rc:
+            self.ctx._err(rc)
+        return Reader(self.ctx, ptr)
+
+
 class Reader:
     """sccg_reader: ranges of the target read from a record without rebuilding it.  It owns its
     device memory (independent of later calls on the context); close it before the context."""
@@ -407,6 +504,12 @@ class Reader:
     def length(self) -> int:
         """Bases in the sequence (the FASTA body without its line ends)."""
         return self.lib.sccg_reader_length(self.ptr)
+
+    @property
+    def device_bytes(self) -> int:
+        """The reader's own persistent device allocation (sccg_reader_device_bytes): without R' when
+        it was opened through a Reference."""
+        return self.lib.sccg_reader_device_bytes(self.ptr)
 
     @property
     def header(self) -> bytes:
@@ -521,4 +624,97 @@ class Reader:
         lens = {e - b for b, e in regions}
         if len(lens) == 1 and regions:
             out = out.view(len(regions), lens.pop(), *shape[1:])
+        return out
+
+
+class Cohort:
+    """sccg_cohort: the encoded fetch over many readers of one context, each region naming its sample,
+    in one launch per call.  It keeps references to its Readers but does not own them: close the
+    cohort before them."""
+
+    def __init__(self, readers):
+        self.readers = list(readers)
+        if not self.readers:
+            raise ValueError("a cohort needs at least one reader")
+        self.ctx = self.readers[0].ctx
+        self.lib = self.ctx.lib
+        arr = (ctypes.c_void_p * len(self.readers))(*[r.ptr.value for r in self.readers])
+        self.ptr = ctypes.c_void_p()
+        rc = self.lib.sccg_cohort_create(arr, len(self.readers), ctypes.byref(self.ptr))
+        if rc:
+            self.ctx._err(rc)
+
+    def close(self):
+        if self.ptr:
+            self.lib.sccg_cohort_close(self.ptr)
+            self.ptr = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def samples(self) -> int:
+        return self.lib.sccg_cohort_samples(self.ptr)
+
+    @staticmethod
+    def _items(items):
+        """(sample, begin, end) or (sample, begin, end, reverse) -> sccg_cohort_region array."""
+        items = [tuple(it) for it in items]
+        rows = [(int(it[1]), int(it[2]), int(it[0]), 1 if len(it) > 3 and it[3] else 0) for it in items]
+        return rows, ((CohortRegion * len(rows))(*rows) if rows else None)
+
+    def fetch_encoded(self, items, encoding: str = "index", dtype: str = "u8", revcomp: bool = False, upper: bool = False) -> bytes:
+        """The items' bases concatenated and encoded as Reader.fetch_encoded does (sccg_cohort_fetch).
+        items: (sample, begin, end) or (sample, begin, end, reverse); revcomp: all of them reversed."""
+        rows, arr = self._items(items)
+        fmt = Reader._format(encoding, dtype, revcomp, upper)
+        buf = Buf()
+        rc = self.lib.sccg_cohort_fetch(self.ptr, arr, len(rows), ctypes.byref(fmt), ctypes.byref(buf))
+        if rc:
+            self.ctx._err(rc)
+        return self.ctx._take(buf)
+
+    def fetch_encoded_device(self, items, d_out: int, out_cap: int, encoding: str = "index", dtype: str = "u8",
+                             revcomp: bool = False, upper: bool = False, stream: int = 0) -> int:
+        """fetch_encoded into device memory d_out (capacity out_cap bytes, aligned to the element);
+        returns the bytes written.  d_out = 0 is a size query; a capacity too small raises
+        SCCG_E_NOMEM with the bytes needed in the error's `needed`."""
+        rows, arr = self._items(items)
+        fmt = Reader._format(encoding, dtype, revcomp, upper)
+        n = ctypes.c_size_t()
+        rc = self.lib.sccg_cohort_fetch_device(self.ptr, arr, len(rows), ctypes.byref(fmt), d_out or None, out_cap,
+                                               ctypes.byref(n), stream or None)
+        if rc:
+            err = SccgError(rc, self.lib.sccg_last_error(self.ctx.ptr).decode(errors="replace"))
+            err.needed = n.value
+            raise err
+        return n.value
+
+    def fetch_tensor(self, items, encoding: str = "onehot", dtype=None, revcomp: bool = False, stream=None):
+        """Reader.fetch_tensor over the cohort: [n, L] or [n, L, 4] when every item has the same
+        length L, else flat [F] / [F, 4]."""
+        import torch
+        items = [tuple(it) for it in items]
+        names = {torch.uint8: "u8", torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32"}
+        if encoding != "onehot":
+            dtype = torch.uint8 if dtype is None else dtype
+            if dtype != torch.uint8:
+                raise ValueError(f"{encoding!r} is uint8")
+        elif dtype is None:
+            dtype = torch.float16
+        if dtype not in names:
+            raise ValueError(f"dtype {dtype}: one of {list(names)}")
+        dev = torch.device("cuda", self.ctx.device)
+        F = sum(int(it[2]) - int(it[1]) for it in items)
+        shape = (F, 4) if encoding == "onehot" else (F,)
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        self.fetch_encoded_device(items, out.data_ptr(), out.numel() * out.element_size(), encoding, names[dtype], revcomp,
+                                  stream=s.cuda_stream)
+        lens = {int(it[2]) - int(it[1]) for it in items}
+        if len(lens) == 1 and items:
+            out = out.view(len(items), lens.pop(), *shape[1:])
         return out

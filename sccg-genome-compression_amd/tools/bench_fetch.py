@@ -11,7 +11,15 @@ the profiler's "fetch" family.  sccg_reconstruct_device on the same pair in the 
 yardstick.  Then sccg_reader_fetch_encoded_device at 1000 x 1 kb and 100,000 x 100 b -- index, one-hot
 f16 and f32, ASCII with alternating strands -- each beside the two-step path it replaces: the ASCII
 fetch of the same regions followed by a PyTorch lookup-table encode to the same dtype on the same
-stream.  Every shape's bytes are checked against the target FASTA.  Prints one JSON line
+stream.  Then the cohort: S = 8 readers opened through one shared reference -- the SAME record eight
+times, because the generator makes reference and target from one seed and cannot hold the reference
+fixed under another target; the kernel's per-span choice of the source is the same -- and a batch
+of 1000 x 1 kb and of 100,000 x 100 b spread evenly over the samples in random order, index and
+one-hot f16, interleaved call by call: (a) one sccg_cohort_fetch_device, (b) S
+sccg_reader_fetch_encoded_device calls of the same regions grouped by sample, (c) the same total
+shape from one reader in one call, and (a1) the cohort call over ONE reader listed S times, which
+keeps (a)'s per-span descriptor reads and (c)'s memory footprint; with the readers' device bytes and
+open times, private against shared.  Every shape's bytes are checked against the target FASTA.  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
 import ctypes
@@ -29,6 +37,113 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def spread(ts):
     return {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)}
+
+
+def cohort_section(a, ctx, lib, torch, sccg, dev, stream, rd, d_ref, ref_len, d_rec, rec_len, truth, code, S=8):
+    """Memory and open time, private against shared; then (a) / (b) / (c) interleaved."""
+    s = stream.cuda_stream
+    L = rd.length
+    out = {"samples": S, "same_record": True}
+
+    def opened(fn, close=True):
+        ts, h = [], None
+        for _ in range(3):
+            if h is not None and close:
+                h.close()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            h = fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return h, spread(ts)
+
+    ref, out["reference_open_ms"] = opened(lambda: ctx.open_reference_device(d_ref.data_ptr(), ref_len, stream=s))
+    prv, out["open_private_ms"] = opened(lambda: ctx.open_reader_device(d_ref.data_ptr(), ref_len, d_rec.data_ptr(), rec_len, s))
+    sh0, out["open_shared_ms"] = opened(lambda: ref.open_reader_device(d_rec.data_ptr(), rec_len, s))
+    readers = [sh0] + [ref.open_reader_device(d_rec.data_ptr(), rec_len, s) for _ in range(S - 1)]
+    out["reader_device_bytes"] = {"private": prv.device_bytes, "shared": sh0.device_bytes, "reference": ref.device_bytes,
+                                  f"{S}_private": S * prv.device_bytes, f"{S}_shared_plus_reference": S * sh0.device_bytes + ref.device_bytes}
+    prv.close()
+    co = sccg.Cohort(readers)
+    co1 = sccg.Cohort([readers[0]] * S)   # S table entries, one reader's memory: the descriptor reads without the S-fold footprint
+    rng = random.Random(2)
+    codes = np.array(code, dtype=np.uint8)
+    out["fetch"] = {}
+    for name, (n, ln) in {"1000x1kb": (1000, 1000), "100000x100b": (100_000, 100)}.items():
+        begins = [rng.randrange(L - ln) for _ in range(n)]
+        samp = [k % S for k in range(n)]
+        rng.shuffle(samp)
+        F = n * ln
+        items = (sccg.CohortRegion * n)(*[(b, b + ln, sm, 0) for b, sm in zip(begins, samp)])
+        flat = (sccg.Region * n)(*[(b, b + ln) for b in begins])
+        groups = [[b for b, sm in zip(begins, samp) if sm == k] for k in range(S)]
+        garr = [(sccg.Region * len(g))(*[(b, b + ln) for b in g]) for g in groups]
+        fwd = b"".join(truth[b:b + ln] for b in begins)
+        grouped = b"".join(truth[b:b + ln] for g in groups for b in g)
+        for row, (enc, dt, bpb) in {"index": ("index", "u8", 1), "onehot_f16": ("onehot", "f16", 8)}.items():
+            fmt = sccg.FetchFormat(sccg.ENCODINGS[enc], sccg.DTYPES[dt], 0, 0)
+            d_o = [torch.empty(F * bpb + 64, dtype=torch.uint8, device=dev) for _ in range(4)]
+            got = ctypes.c_size_t()
+
+            def call_a():
+                rc = lib.sccg_cohort_fetch_device(co.ptr, items, n, ctypes.byref(fmt), d_o[0].data_ptr(), F * bpb, ctypes.byref(got), s)
+                assert rc == 0 and got.value == F * bpb, (rc, got.value)
+
+            def call_b():
+                at = 0
+                for k in range(S):
+                    nb = len(groups[k]) * ln * bpb
+                    rc = lib.sccg_reader_fetch_encoded_device(readers[k].ptr, garr[k], len(groups[k]), None, ctypes.byref(fmt),
+                                                              d_o[1].data_ptr() + at, nb, ctypes.byref(got), s)
+                    assert rc == 0 and got.value == nb, (rc, got.value)
+                    at += nb
+
+            def call_c():
+                rc = lib.sccg_reader_fetch_encoded_device(readers[0].ptr, flat, n, None, ctypes.byref(fmt), d_o[2].data_ptr(), F * bpb,
+                                                          ctypes.byref(got), s)
+                assert rc == 0 and got.value == F * bpb, (rc, got.value)
+
+            def call_a1():
+                rc = lib.sccg_cohort_fetch_device(co1.ptr, items, n, ctypes.byref(fmt), d_o[3].data_ptr(), F * bpb, ctypes.byref(got), s)
+                assert rc == 0 and got.value == F * bpb, (rc, got.value)
+
+            calls = {"a_cohort": call_a, "b_per_sample": call_b, "c_one_reader": call_c, "a1_cohort_of_one_reader": call_a1}
+            ev = {k: [] for k in calls}
+            for i in range(a.warmup + a.calls):   # interleaved: a, b, c, a, b, c, ...
+                for k, call in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    e0.record(stream)
+                    call()
+                    e1.record(stream)
+                    stream.synchronize()
+                    if i >= a.warmup:
+                        ev[k].append(e0.elapsed_time(e1))
+            ctx.profile(True, families=["fetch"])
+            for _ in range(a.calls):
+                call_a()
+            kern = ctx.profile_get().get("fetch", (0.0, 0))
+            ctx.profile(False)
+
+            def encoded(seq):
+                c = codes[np.frombuffer(seq, dtype=np.uint8)]
+                return c.tobytes() if enc == "index" else np.vstack([np.eye(4), np.zeros((1, 4))]).astype(np.float16)[c].tobytes()
+
+            w_flat, w_grouped = encoded(fwd), encoded(grouped)
+            exact = [d_o[0][:F * bpb].cpu().numpy().tobytes() == w_flat, d_o[1][:F * bpb].cpu().numpy().tobytes() == w_grouped,
+                     d_o[2][:F * bpb].cpu().numpy().tobytes() == w_flat, d_o[3][:F * bpb].cpu().numpy().tobytes() == w_flat]
+            med = {k: statistics.median(v) for k, v in ev.items()}
+            out["fetch"][f"{name}/{row}"] = {
+                "bytes": F * bpb, "event_ms": {k: spread(v) for k, v in ev.items()},
+                "kernel_ms_mean": round(kern[0] / max(kern[1], 1), 4), "launches_per_call": kern[1] / a.calls,
+                "b_over_a": round(med["b_per_sample"] / med["a_cohort"], 2), "a_over_c": round(med["a_cohort"] / med["c_one_reader"], 3),
+                "exact": all(exact)}
+            del d_o
+    co.close()
+    co1.close()
+    for r in readers:
+        r.close()
+    ref.close()
+    return out
 
 
 def main() -> None:
@@ -190,9 +305,13 @@ def main() -> None:
                 "two_step_over_encoded": round(med2 / med, 2)}
             del d_o
         del d_a
+    if hasattr(lib, "sccg_cohort_fetch_device"):   # (absent from a library older than the cohort fetch)
+        out["cohort"] = cohort_section(a, ctx, lib, torch, sccg, dev, stream, rd, d_ref, len(rfa), d_rec, len(rec_h), truth, code)
     rd.close()
     ctx.close()
     print(json.dumps(out))
+    if "cohort" in out and not all(v["exact"] for v in out["cohort"]["fetch"].values()):
+        raise SystemExit("bench_fetch: cohort bytes differ from the target FASTA")
     if not all(v["exact"] and v["two_step_exact"] for v in out["fetch_encoded"].values()):
         raise SystemExit("bench_fetch: encoded bytes differ from the target FASTA")
     if not all(v["exact"] for v in out["fetch"].values()):
