@@ -201,6 +201,32 @@ __device__ __forceinline__ T block_excl_add(T v, T* tmp, T* total) {
     return r;
 }
 
+// A grid's arrival ticket: the block that arrives last runs the tail that would otherwise be a
+// launch of its own (no block waits for another).  The whole block calls it after its global
+// stores; it returns true in the last block only, whose loads from then on see every block's
+// stores.  Producer side: every wave drains its stores, the block meets, thread 0 releases at agent
+// scope (the L2s of the XCDs are not coherent) and takes the ticket; the last taker acquires before
+// the block goes on.  (The explicit waits: the compiler may drop a fence's own wait.)
+// *ticket is 0 before the launch and is 0 again when the last block returns from here; it belongs
+// to one context's scratch, since two contexts' launches run at once.  lds: one LDS word.
+__device__ __forceinline__ bool grid_last_block(unsigned int* ticket, int* lds) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const bool last = atomicAdd(ticket, 1u) == gridDim.x * gridDim.y - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            atomicExch(ticket, 0u);
+        }
+        *lds = last;
+    }
+    __syncthreads();
+    return *lds != 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // HIP error plumbing (host side)
 // ---------------------------------------------------------------------------------------------

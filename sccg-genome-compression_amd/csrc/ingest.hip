@@ -427,10 +427,12 @@ __device__ __forceinline__ TileSum ts_shfl_up(const TileSum& v, int d) {
     return r;
 }
 
-// Scan of the tile summaries in three launches.  (1) one thread per tile, 1024 tiles per block:
-// block-local exclusive prefix, written over the tile's own summary, and the block total;
-// (2) one block: exclusive prefix of the block totals; (3) per tile: stream prefix = "carry 1"
-// then block prefix then local prefix -> output offsets (strip and filter) and carry-in status.
+// Scan of the tile summaries in one launch (k_strip_scan).  One thread per SCAN_PER tiles, 1024
+// tiles per block: the block-local exclusive prefix, written over the tiles' own summaries, and the
+// block total; the block that arrives last (grid_last_block) turns the block totals into their
+// exclusive prefix and writes the stream's lengths.  The write pass composes each tile's stream
+// prefix itself: "carry 1" then block prefix then local prefix -> output offsets (strip and filter)
+// and carry-in status.
 constexpr int SCAN_B = 1024;
 __device__ __forceinline__ TileSum block_scan_tiles(TileSum v, TileSum* wsum, TileSum* total) {
     const TileSum id{0, 0, 0, 0, -1};
@@ -456,36 +458,40 @@ __device__ __forceinline__ TileSum block_scan_tiles(TileSum v, TileSum* wsum, Ti
 }
 
 // (SCAN_T threads per block, SCAN_B / SCAN_T tiles per thread.  A 1024-thread block waits for
-// a whole free CU -- the target's scan sat ~140 us behind the reference strip's write pass on the
-// side stream in a chr1 trace -- but 256-thread builds measured within noise end to end.)
-constexpr int SCAN_T = 1024, SCAN_PER = SCAN_B / SCAN_T;
-__global__ __launch_bounds__(SCAN_T) void k_strip_scan_local(int64_t ntiles, int64_t* __restrict__ ta, int64_t* __restrict__ tb,
-                                                          int64_t* __restrict__ tfa, int64_t* __restrict__ tfb,
-                                                          int32_t* __restrict__ tlast, TileSum* __restrict__ btot) {
+// a whole free CU -- the target's scan sat ~80-140 us behind the reference strip's write pass on
+// the side stream in chr1 traces -- so the blocks are 256 threads.)
+constexpr int SCAN_T = 256, SCAN_PER = SCAN_B / SCAN_T;
+__global__ __launch_bounds__(SCAN_T) void k_strip_scan(int64_t ntiles, int64_t* __restrict__ ta, int64_t* __restrict__ tb,
+                                                    int64_t* __restrict__ tfa, int64_t* __restrict__ tfb,
+                                                    int32_t* __restrict__ tlast, TileSum* __restrict__ btot,
+                                                    unsigned int* __restrict__ ticket, int64_t* __restrict__ d_len,
+                                                    int64_t* __restrict__ d_len2) {
     __shared__ TileSum wsum[17];
+    __shared__ int last;
     const TileSum id{0, 0, 0, 0, -1};
-    const int64_t t0 = (int64_t)blockIdx.x * SCAN_B + (int64_t)threadIdx.x * SCAN_PER;
-    TileSum v[SCAN_PER], agg = id;
+    {
+        const int64_t t0 = (int64_t)blockIdx.x * SCAN_B + (int64_t)threadIdx.x * SCAN_PER;
+        TileSum v[SCAN_PER], agg = id;
 #pragma unroll
-    for (int k = 0; k < SCAN_PER; k++) {
-        const int64_t t = t0 + k;
-        v[k] = t < ntiles ? TileSum{ta[t], tb[t], tfa[t], tfb[t], tlast[t]} : id;
-        agg = ts_compose(agg, v[k]);
-    }
-    TileSum tot;
-    TileSum run = block_scan_tiles(agg, wsum, &tot);
+        for (int k = 0; k < SCAN_PER; k++) {
+            const int64_t t = t0 + k;
+            v[k] = t < ntiles ? TileSum{ta[t], tb[t], tfa[t], tfb[t], tlast[t]} : id;
+            agg = ts_compose(agg, v[k]);
+        }
+        TileSum tot;
+        TileSum run = block_scan_tiles(agg, wsum, &tot);
 #pragma unroll
-    for (int k = 0; k < SCAN_PER; k++) {
-        const int64_t t = t0 + k;
-        if (t < ntiles) { ta[t] = run.a; tb[t] = run.b; tfa[t] = run.fa; tfb[t] = run.fb; tlast[t] = run.last; }
-        run = ts_compose(run, v[k]);
+        for (int k = 0; k < SCAN_PER; k++) {
+            const int64_t t = t0 + k;
+            if (t < ntiles) { ta[t] = run.a; tb[t] = run.b; tfa[t] = run.fa; tfb[t] = run.fb; tlast[t] = run.last; }
+            run = ts_compose(run, v[k]);
+        }
+        if (threadIdx.x == 0) btot[blockIdx.x] = tot;
     }
-    if (threadIdx.x == 0) btot[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(SCAN_T) void k_strip_scan_blocks(int64_t nblk, TileSum* __restrict__ btot) {
-    __shared__ TileSum wsum[17];
-    const TileSum id{0, 0, 0, 0, -1};
+    if (!grid_last_block(ticket, &last)) return;
+    // every block's total is in btot (gridDim.x <= SCAN_B of them): their exclusive prefix in place,
+    // the stream's total behind them, and the lengths
+    const int64_t nblk = gridDim.x;
     const int64_t i0 = (int64_t)threadIdx.x * SCAN_PER;
     TileSum v[SCAN_PER], agg = id;
 #pragma unroll
@@ -500,27 +506,24 @@ __global__ __launch_bounds__(SCAN_T) void k_strip_scan_blocks(int64_t nblk, Tile
         if (i0 + k < nblk) btot[i0 + k] = run;
         run = ts_compose(run, v[k]);
     }
-    if (threadIdx.x == 0) btot[SCAN_B] = tot;
-}
-
-__global__ void k_strip_scan_apply(int64_t ntiles, const int64_t* __restrict__ ta, const int64_t* __restrict__ tb,
-                                   const int64_t* __restrict__ tfa, const int64_t* __restrict__ tfb,
-                                   const int32_t* __restrict__ tlast, const TileSum* __restrict__ btot,
-                                   int64_t* __restrict__ toff, int64_t* __restrict__ toff2, int32_t* __restrict__ tcarry,
-                                   int64_t* __restrict__ d_len, int64_t* __restrict__ d_len2) {
-    const TileSum start{0, 0, 0, 0, 1};   // the stream starts as if after a kept line
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < ntiles; t += (int64_t)gridDim.x * blockDim.x) {
-        const TileSum r = ts_compose(ts_compose(start, btot[t / SCAN_B]), TileSum{ta[t], tb[t], tfa[t], tfb[t], tlast[t]});
-        toff[t] = r.b;
-        toff2[t] = r.fb;
-        tcarry[t] = r.last;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const TileSum r = ts_compose(start, btot[SCAN_B]);
+    if (threadIdx.x == 0) {
+        btot[SCAN_B] = tot;
+        const TileSum r = ts_compose(TileSum{0, 0, 0, 0, 1}, tot);   // the stream starts as if after a kept line
         *d_len = r.b;
         if (d_len2) *d_len2 = r.fb;
     }
 }
+
+// What k_strip_write composes a tile's offsets from (k_strip_scan's results); ta null: the offsets
+// of an earlier write pass over the same input are read back instead (launch_strip_rewrite).
+struct StripScan {
+    const int64_t* ta = nullptr;
+    const int64_t* tb = nullptr;
+    const int64_t* tfa = nullptr;
+    const int64_t* tfb = nullptr;
+    const int32_t* tlast = nullptr;
+    const TileSum* btot = nullptr;
+};
 
 // Run events of a lane's kept bytes (RUNS: the target strip emits both run lines' boundaries,
 // compression.cpp:341-368 lowercase and :527-555 N, instead of two more passes over T).  For a
@@ -541,10 +544,9 @@ __device__ __forceinline__ void run_events(uint64_t p, uint64_t K, uint32_t cin,
 
 template <IngestMode MODE, bool RUNS>
 __global__ __launch_bounds__(SCCG_BLOCK) void k_strip_write(FilterMode fm, const uint8_t* __restrict__ buf, int64_t n,
-                                                            const int64_t* __restrict__ hdr,
-                                                            const int64_t* __restrict__ toff,
-                                                            const int64_t* __restrict__ toff2,
-                                                            const int32_t* __restrict__ tcarry,
+                                                            const int64_t* __restrict__ hdr, StripScan sp,
+                                                            int64_t* __restrict__ toff, int64_t* __restrict__ toff2,
+                                                            int32_t* __restrict__ tcarry,
                                                             uint8_t* __restrict__ out, uint8_t* __restrict__ out2,
                                                             int32_t* __restrict__ flags, RunSlots rsl,
                                                             const uint16_t* __restrict__ kc, const int32_t* __restrict__ kflag) {
@@ -559,6 +561,19 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_strip_write(FilterMode fm, const
     uint8_t* s1 = reinterpret_cast<uint8_t*>(st4);
     const int64_t off = tile * STRIP_WTILE + (int64_t)lane * SL;
     const int64_t h = MODE == INGEST_TGT ? hdr[0] : 0, he = MODE == INGEST_TGT ? hdr[1] : 0;
+    // the tile's output offsets and carried-in line status: the stream prefix "carry 1" then the
+    // scan block's prefix then the tile's block-local prefix; lane 0 stores them for the passes
+    // that follow (k_strip_gather, the run lines, a later rewrite)
+    int64_t o1, o2;
+    int32_t carry;
+    if (sp.ta) {
+        const TileSum x = ts_compose(TileSum{0, 0, 0, 0, 1}, sp.btot[tile / SCAN_B]);
+        const TileSum y = ts_compose(x, TileSum{sp.ta[tile], sp.tb[tile], sp.tfa[tile], sp.tfb[tile], sp.tlast[tile]});
+        o1 = y.b; o2 = y.fb; carry = y.last;
+        if (lane == 0) { toff[tile] = o1; toff2[tile] = o2; tcarry[tile] = carry; }
+    } else {
+        o1 = toff[tile]; o2 = toff2[tile]; carry = tcarry[tile];
+    }
     uint32_t w[SNW];
     int32_t prior;
     uint64_t lsm;
@@ -567,7 +582,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_strip_write(FilterMode fm, const
     // instead of classifying its bytes again, unless they depend on a carried-in line status other
     // than "keep"
     const int32_t kf = kc ? uni(kflag[tile]) : 0;
-    if ((kf & 1) && (MODE == INGEST_TGT || !(kf & 2) || uni(tcarry[tile]) == 1)) {
+    if ((kf & 1) && (MODE == INGEST_TGT || !(kf & 2) || uni(carry) == 1)) {
         load_words<SNW>(buf, n, off, w);
         const uint32_t code = kc[tile * 64 + lane], h1 = code & 127u, h2 = code >> 7;
         const uint64_t keep = ~((h1 < 64 ? 1ull << h1 : 0ull) | (h2 < 64 ? 1ull << h2 : 0ull));
@@ -575,7 +590,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_strip_write(FilterMode fm, const
         prior = 1;
     } else {
         r = strip_tile<MODE, RUNS>(fm, buf, n, h, he, off, w, prior, lsm, stage_all4[wave_in_block()]);
-        if (MODE == INGEST_REF && prior < 0) prior = tcarry[tile];
+        if (MODE == INGEST_REF && prior < 0) prior = carry;
     }
     const uint64_t keep = r.known | (prior == 1 ? r.unknown : 0ull), fkeep = keep & r.fk;
     const uint32_t c = (uint32_t)__popcll(keep) | ((uint32_t)__popcll(fkeep) << 16);
@@ -613,7 +628,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_strip_write(FilterMode fm, const
             rsl.rf[tile] = (hm ? 1 : 0) | (int32_t)(tf << 1) | (int32_t)(tl << 3);
         }
         if ((sl | el | sn | en) != 0) {   // (rare: a lane holds ~0.1 run boundaries)
-            const int64_t o0 = toff[tile] + (int64_t)(ex & 0xffff);
+            const int64_t o0 = o1 + (int64_t)(ex & 0xffff);
             int32_t* const dst[4] = {rsl.sl, rsl.el, rsl.sn, rsl.en};
             const uint64_t ev[4] = {sl, el, sn, en};
 #pragma unroll
@@ -632,16 +647,16 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_strip_write(FilterMode fm, const
     if (out) {   // (null: only the filtered copy is wanted -- the reconstruction needs R' alone)
         stage_lane<false>(s1, tab, w, keep, (int)(ex & 0xffff));
         wave_sync();
-        stage_out(st4, (int)(tot & 0xffff), out, toff[tile]);
+        stage_out(st4, (int)(tot & 0xffff), out, o1);
     }
     if (out2) {
         if (out && !__ballot(fkeep != keep)) {   // the filter dropped nothing here: same bytes, uppercased
-            stage_out<true>(st4, (int)(tot >> 16), out2, toff2[tile]);
+            stage_out<true>(st4, (int)(tot >> 16), out2, o2);
         } else {
             wave_sync();
             stage_lane<true>(s1, tab, w, fkeep, (int)(ex >> 16));
             wave_sync();
-            stage_out(st4, (int)(tot >> 16), out2, toff2[tile]);
+            stage_out(st4, (int)(tot >> 16), out2, o2);
         }
     }
 }
@@ -887,9 +902,13 @@ __global__ void k_run_textwrite(const int32_t* __restrict__ rs, const int32_t* _
 // a target without one is scanned to its end by this block, ~1 us per 16 KiB).  It replaces an
 // init launch and two 64-block ticket searches, which in multi-context runs waited ~50 us each for
 // CU slots behind the other context's grids.  d_sc[0] = header start (n: none), d_sc[1] = its '\n'
-// (n: none), d_sc[2..3] = 0.
+// (n: none), d_sc[2..3] = 0.  As the first launch of a compression's main stream it also resets the
+// call's other scalars, which were set and memset launches of their own: the local pass's control
+// words d_sc[20..21] = {0, none yet | none yet}, the '(' flag word at d_sc[32], and the run slots'
+// overflow flag (ovf, or null).
 constexpr int FH_T = 256, FH_PER = 64;   // (a 1024-thread block would wait for a whole free CU)
-__global__ __launch_bounds__(FH_T) void k_find_header(const uint8_t* __restrict__ buf, int64_t n, int64_t* __restrict__ d_sc) {
+__global__ __launch_bounds__(FH_T) void k_find_header(const uint8_t* __restrict__ buf, int64_t n, int64_t* __restrict__ d_sc,
+                                                      int32_t* __restrict__ ovf) {
     __shared__ unsigned long long s_hit;
     int64_t res[2] = {n, n};
     for (int ph = 0; ph < 2; ph++) {
@@ -920,7 +939,13 @@ __global__ __launch_bounds__(FH_T) void k_find_header(const uint8_t* __restrict_
             if (h != ~0ull) { res[ph] = (int64_t)h; break; }
         }
     }
-    if (threadIdx.x == 0) { d_sc[0] = res[0]; d_sc[1] = res[1]; d_sc[2] = 0; d_sc[3] = 0; }
+    if (threadIdx.x == 0) {
+        d_sc[0] = res[0]; d_sc[1] = res[1]; d_sc[2] = 0; d_sc[3] = 0;
+        d_sc[20] = (int64_t)INT32_MAX << 32;
+        d_sc[21] = (int64_t)INT32_MAX;
+        *reinterpret_cast<int32_t*>(d_sc + 32) = 0;
+        if (ovf) *ovf = 0;
+    }
 }
 
 // =============================================================================================
@@ -937,10 +962,8 @@ int launch_first_match(const uint8_t* buf, int64_t n, const int64_t* from_slot, 
     return 0;
 }
 
-int launch_find_header(const uint8_t* buf, int64_t n, int64_t* d_sc, hipStream_t s) {
-    // d_sc[0] = header start (first '>' at a line start), d_sc[1] = its '\n' (n if none);
-    // d_sc[2], d_sc[3] are the chunk tickets (free for the caller afterwards); one init launch
-    hipLaunchKernelGGL(k_find_header, dim3(1), dim3(FH_T), 0, s, buf, n, d_sc);
+int launch_find_header(const uint8_t* buf, int64_t n, int64_t* d_sc, int32_t* d_ovf, hipStream_t s) {
+    hipLaunchKernelGGL(k_find_header, dim3(1), dim3(FH_T), 0, s, buf, n, d_sc, d_ovf);
     SCCG_HIP(hipGetLastError());
     return 0;
 }
@@ -969,21 +992,18 @@ int launch_fasta_strip(IngestMode mode, const uint8_t* buf, int64_t n, const int
     const int64_t nblk = (ntiles + SCAN_B - 1) / SCAN_B;
     if (nblk > SCAN_B) return SCCG_E_UNSUPPORTED;   // > 4 GiB of FASTA
     TileSum* btot = reinterpret_cast<TileSum*>(sc.block_sums);
-    hipLaunchKernelGGL(k_strip_scan_local, dim3((unsigned)nblk), dim3(SCAN_T), 0, s, ntiles, sc.tile_a, sc.tile_b,
-                       sc.tile_fa, sc.tile_fb, sc.tile_last, btot);
-    hipLaunchKernelGGL(k_strip_scan_blocks, dim3(1), dim3(SCAN_T), 0, s, nblk, btot);
-    hipLaunchKernelGGL(k_strip_scan_apply, dim3(grid_for(ntiles, 256)), dim3(256), 0, s, ntiles, sc.tile_a, sc.tile_b,
-                       sc.tile_fa, sc.tile_fb, sc.tile_last, btot, sc.tile_off, sc.tile_off2, sc.tile_carry, d_len,
-                       d_len2);
+    hipLaunchKernelGGL(k_strip_scan, dim3((unsigned)nblk), dim3(SCAN_T), 0, s, ntiles, sc.tile_a, sc.tile_b, sc.tile_fa,
+                       sc.tile_fb, sc.tile_last, btot, sc.scan_ticket, d_len, d_len2);
+    const StripScan sp{sc.tile_a, sc.tile_b, sc.tile_fa, sc.tile_fb, sc.tile_last, btot};
     const RunSlots rsl = runs ? *runs : RunSlots{};
     if (mode == INGEST_TGT && runs)
-        PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_TGT, true>), dim3(g), dim3(SCCG_BLOCK), 0, s, fmode, buf, n, d_header,
+        PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_TGT, true>), dim3(g), dim3(SCCG_BLOCK), 0, s, fmode, buf, n, d_header, sp,
                     sc.tile_off, sc.tile_off2, sc.tile_carry, out, out2, d_flags, rsl, (const uint16_t*)kc, (const int32_t*)kf);
     else if (mode == INGEST_TGT)
-        PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_TGT, false>), dim3(g), dim3(SCCG_BLOCK), 0, s, fmode, buf, n, d_header,
+        PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_TGT, false>), dim3(g), dim3(SCCG_BLOCK), 0, s, fmode, buf, n, d_header, sp,
                     sc.tile_off, sc.tile_off2, sc.tile_carry, out, out2, d_flags, rsl, (const uint16_t*)kc, (const int32_t*)kf);
     else
-        PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_REF, false>), dim3(g), dim3(SCCG_BLOCK), 0, s, fmode, buf, n, d_header,
+        PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_REF, false>), dim3(g), dim3(SCCG_BLOCK), 0, s, fmode, buf, n, d_header, sp,
                     sc.tile_off, sc.tile_off2, sc.tile_carry, out, out2, d_flags, rsl, (const uint16_t*)kc, (const int32_t*)kf);
     SCCG_HIP(hipGetLastError());
     return 0;
@@ -1059,11 +1079,11 @@ int launch_strip_rewrite(IngestMode mode, const uint8_t* buf, int64_t n, const i
     const RunSlots rsl{};
     if (mode == INGEST_TGT)
         PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_TGT, false>), dim3(g), dim3(SCCG_BLOCK), 0, s, FILTER_UPPER, buf, n,
-                    d_header, sc.tile_off, sc.tile_off2, sc.tile_carry, out, (uint8_t*)nullptr, (int32_t*)nullptr, rsl,
+                    d_header, StripScan{}, sc.tile_off, sc.tile_off2, sc.tile_carry, out, (uint8_t*)nullptr, (int32_t*)nullptr, rsl,
                     (const uint16_t*)nullptr, (const int32_t*)nullptr);
     else
         PROF_LAUNCH(PROF_STRIP, s, (k_strip_write<INGEST_REF, false>), dim3(g), dim3(SCCG_BLOCK), 0, s, FILTER_UPPER, buf, n,
-                    d_header, sc.tile_off, sc.tile_off2, sc.tile_carry, out, (uint8_t*)nullptr, (int32_t*)nullptr, rsl,
+                    d_header, StripScan{}, sc.tile_off, sc.tile_off2, sc.tile_carry, out, (uint8_t*)nullptr, (int32_t*)nullptr, rsl,
                     (const uint16_t*)nullptr, (const int32_t*)nullptr);
     SCCG_HIP(hipGetLastError());
     return 0;

@@ -79,14 +79,17 @@ struct IngestScratch {
     int64_t* tile_off2;
     int32_t* tile_carry;
     void* block_sums;     // (1024 + 1) x 40 bytes
+    unsigned int* scan_ticket = nullptr;   // the scan's arrival ticket: 0 between launches (zeroed with its buffer)
     int64_t* scalars;     // [0] header start, [1] header end, [2] out len, [3] flags
     uint16_t* keep_cache = nullptr;   // per tile 64 lanes' unkept-byte codes, or null: the write pass classifies every tile
     int32_t* keep_flag = nullptr;     // per tile (k_strip_summary)
 };
 
 // Target header: first line starting with '>' (compression.cpp:210); writes [h, he) into
-// scalars[0..1] (h = n when absent).
-int launch_find_header(const uint8_t* buf, int64_t n, int64_t* d_scalars, hipStream_t s);
+// scalars[0..1] (h = n when absent).  The same launch resets the compression call's scalars: [2..3] = 0,
+// [20..21] = the local pass's control words (no bound, no switch yet), the flag word at [32] = 0, and
+// *d_ovf = 0 (the run slots' overflow flag; may be null).  d_scalars holds >= 33 words.
+int launch_find_header(const uint8_t* buf, int64_t n, int64_t* d_scalars, int32_t* d_ovf, hipStream_t s);
 // *res = first position >= *from_slot + 1 (0 if from_slot is null) holding byte c (mode 1) or a
 // '>' that starts a line (mode 0); n if none.  *ticket_slot is scratch.
 int launch_first_match(const uint8_t* buf, int64_t n, const int64_t* from_slot, int mode, uint8_t c, int64_t* res,
@@ -207,11 +210,14 @@ void global_prepare_reset();   // forget a preparation that will not be used
 // the target's first k-mer, read from the target FASTA (d_hdr: its header range).  A later
 // global_prepare on the same ws/R' only extends those positions once T' exists.  |R'| is read on
 // the device from d_nRp (no host round trip); nRp_bound >= |R'| sizes the workspace and the anchor
-// table (ws must hold walk_workspace_bytes(nRp_bound, tn, ...)).
+// table (ws must hold walk_workspace_bytes(nRp_bound, tn, ...)).  What needs no R' (the table's
+// occasional clear, the counters, the first k-mer) is queued on s_head, which need not wait for R';
+// ev_head is recorded behind it and s waits for it just ahead of the sweep.
 // the workspace at ws is freed (sccg_ctx::get, sccg_ctx_destroy): forget its anchor-table generations
 void walk_forget_workspace(const void* ws);
 int global_sweep_early(const uint8_t* Rp, int64_t nRp_bound, const int64_t* d_nRp, const uint8_t* tgt_fa, int64_t tn,
-                       const int64_t* d_hdr, int k, int m, int chunk, void* ws, size_t ws_bytes, hipStream_t s);
+                       const int64_t* d_hdr, int k, int m, int chunk, void* ws, size_t ws_bytes, hipStream_t s_head,
+                       hipEvent_t ev_head, hipStream_t s);
 // Where the record text goes, when the caller learns it only during the walk: resolve() is called
 // once, after the rounds and before the text is written, and returns the output pointer.
 struct EmitTarget {

@@ -160,7 +160,7 @@ struct sccg_ctx {
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr;       // walk preparation, overlapping the local pass
     hipStream_t side2 = nullptr;      // header + run lines, overlapping the local pass
-    hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join = nullptr, ev_lines = nullptr, ev_rstrip = nullptr, ev_hdr = nullptr, ev_tstrip = nullptr,
+    hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join = nullptr, ev_lines = nullptr, ev_rstrip = nullptr, ev_hdr = nullptr, ev_kmer = nullptr, ev_tstrip = nullptr,
                ev_local = nullptr, ev_probe = nullptr;
     int64_t* h_switch = nullptr;      // pinned: the local pass's switch word, copied behind the pass
     int32_t* h_probe = nullptr;       // pinned: the switch probe's classes and segments (2 PROBE_PAIRS)
@@ -168,6 +168,7 @@ struct sccg_ctx {
     sccg_stats stats{};
     void* buf[B_COUNT] = {};
     size_t cap[B_COUNT] = {};
+    bool fresh[B_COUNT] = {};   // allocated since its user last looked (a buffer that keeps state between calls)
     // sccg_compress_files: pinned staging slots (STAGE_THREADS readers x STAGE_SLOTS), one copy
     // stream per input file, allocated on first use
     uint8_t* stage[16] = {};
@@ -211,6 +212,7 @@ struct sccg_ctx {
         }
         buf[slot] = p;
         cap[slot] = bytes;
+        fresh[slot] = true;
         return p;
     }
 };
@@ -298,6 +300,7 @@ int sccg_ctx_create(int device, sccg_ctx** out) {
         hipEventCreateWithFlags(&c->ev_tstrip, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_rstrip, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_hdr, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_kmer, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_local, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_probe, hipEventDisableTiming) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&c->h_probe), 2 * PROBE_PAIRS * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
@@ -326,6 +329,7 @@ void sccg_ctx_destroy(sccg_ctx* ctx) {
     (void)hipEventDestroy(ctx->ev_tstrip);
     (void)hipEventDestroy(ctx->ev_rstrip);
     (void)hipEventDestroy(ctx->ev_hdr);
+    (void)hipEventDestroy(ctx->ev_kmer);
     (void)hipEventDestroy(ctx->ev_local);
     if (ctx->ev_probe) (void)hipEventDestroy(ctx->ev_probe);
     if (ctx->h_probe) (void)hipHostFree(ctx->h_probe);
@@ -410,9 +414,15 @@ int strip(sccg_ctx* ctx, IngestMode mode, const uint8_t* fa, int64_t n, const in
     // 64 FASTA bytes, written by the summary and read back instead of classifying plain tiles again
     static const bool kc_on = [] { const char* e = getenv("SCCG_STRIP_KC"); return !e || atoi(e) > 0; }();
     constexpr int64_t KC_AT = 5152;   // (int64s: 1025 x 5 rounded up to 256 bytes)
-    GET(int64_t, bs, B_TILE_BSUM + o, kc_on ? KC_AT + ntiles * 16 + (ntiles + 1) / 2 : 1025 * 5);
+    constexpr int64_t TICKET_AT = 5128;   // the scan's arrival ticket, in that rounding's slack
+    GET(int64_t, bs, B_TILE_BSUM + o, kc_on ? KC_AT + ntiles * 16 + (ntiles + 1) / 2 : KC_AT);
+    if (ctx->fresh[B_TILE_BSUM + o]) {   // the ticket starts at 0; every scan leaves it 0 again
+        HIPTRY(hipMemsetAsync(bs + TICKET_AT, 0, sizeof(int64_t), s ? s : ctx->stream));
+        ctx->fresh[B_TILE_BSUM + o] = false;
+    }
     sc.tile_a = ta; sc.tile_b = tb; sc.tile_fa = tfa; sc.tile_fb = tfb; sc.tile_last = tl; sc.tile_off = to;
     sc.tile_off2 = to2; sc.tile_carry = tc; sc.block_sums = bs; sc.scalars = nullptr;
+    sc.scan_ticket = reinterpret_cast<unsigned int*>(bs + TICKET_AT);
     if (kc_on) {
         sc.keep_cache = reinterpret_cast<uint16_t*>(bs + KC_AT);
         sc.keep_flag = reinterpret_cast<int32_t*>(bs + KC_AT + ntiles * 16);
@@ -557,10 +567,14 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
     const int64_t iters_max = ((rn < tn ? rn : tn) + SEG_L - 1) / SEG_L;   // FASTA lengths bound the sequences'
     const bool probe_mode = !force_global && !ctx->exact_switch && iters_max > 0 && local_probe_applies(iters_max);
     const bool lean_R = probe_mode || force_global;
+    // the '(' flag word, and the local pass control {0, early-exit bound, switch segment, 0} at
+    // sc[20..21] (INT32_MAX = none yet): the header search's launch resets them, and the run slots'
+    // overflow flag
     int32_t* d_flags = reinterpret_cast<int32_t*>(sc + 32);
-    HIPTRY(hipMemsetAsync(d_flags, 0, sizeof(int32_t), s));
-    // local pass control {0, early-exit bound, switch segment, 0}: INT32_MAX = none yet
-    TRY(dev_set_i64(sc + 20, 2, {(int64_t)INT32_MAX << 32, (int64_t)INT32_MAX}, s));
+    // the target strip also emits both run lines' boundaries (RunSlots): no extra passes over T
+    StripRuns sruns;
+    const bool have_runs = strip_runs(ctx, tn, &sruns);
+    int32_t* const d_ovf = have_runs ? sruns.rs.ovf : nullptr;
 
     // ---- ingest (compression.cpp:181-220)
     // header search and both strips run back to back; one sync reads every length (sc[0..9])
@@ -570,7 +584,7 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
     // behind the reference strip's grid it waited ~85 us for issue slots on the chr1 pair, and the
     // target strip -- on the walk's critical path -- waits for it.
     HIPTRY(hipEventRecord(ctx->ev_fork, s));   // (the side stream forks before the search: no wait on it)
-    if (!rdy) TRY(launch_find_header(tfa, tn, sc, s));
+    if (!rdy) TRY(launch_find_header(tfa, tn, sc, d_ovf, s));
     HIPTRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
     if (rdy) {
         hipEvent_t e = nullptr;
@@ -584,13 +598,24 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
         hipEvent_t e = nullptr;
         if (const int rc = rdy->tgt(rdy->user, &e)) return rc;
         HIPTRY(hipStreamWaitEvent(s, e, 0));
-        TRY(launch_find_header(tfa, tn, sc, s));
+        TRY(launch_find_header(tfa, tn, sc, d_ovf, s));
     }
     HIPTRY(hipEventRecord(ctx->ev_hdr, s));
-    // the target strip also emits both run lines' boundaries (RunSlots): no extra passes over T
-    StripRuns sruns;
-    const bool have_runs = strip_runs(ctx, tn, &sruns);
-    if (have_runs) HIPTRY(hipMemsetAsync(sruns.rs.ovf, 0, sizeof(int32_t), s));
+    // The walk's R'-only preparation (anchor samples, positions of the target's first k-mer read off
+    // its FASTA) starts on the side stream as soon as R' exists, beside the target's strip.
+    // The walk workspace is sized by the FASTA lengths (>= |R'|, |T'|), so the early sweep needs no
+    // host read of |R'| (it reads it on the device) and the walk reuses the same carve.
+    // What of it needs only the target FASTA and its header range (the table's occasional clear, the
+    // counters, the first k-mer) goes on side2, idle until the strips end: behind the reference
+    // strip it sat on the sweep's critical path.
+    const size_t wsb = walk_workspace_bytes(rn, tn, kg, walk_chunk(tn));
+    if (rn < INT32_MAX - 8 && tn < INT32_MAX - 8) {
+        HIPTRY(hipStreamWaitEvent(ctx->side2, ctx->ev_hdr, 0));
+        void* ws_early = ctx->get(B_WALK, wsb);
+        if (!ws_early) return ctx->fail(SCCG_E_NOMEM, "walk workspace of %zu bytes", wsb);
+        TRY(global_sweep_early(Rp, rn, sc + 8, tfa, tn, sc, kg, mg, walk_chunk(tn), ws_early, wsb, ctx->side2, ctx->ev_kmer,
+                               ctx->side));
+    }
     const bool lean_T = lean_R && have_runs;   // (without run-event slots the run lines read T)
     TRY(strip(ctx, INGEST_TGT, tfa, tn, sc, lean_T ? nullptr : T, sc + 2, d_flags, nullptr, FILTER_DROP_N_UPPER, Tp, 0,
               nullptr, have_runs ? &sruns.rs : nullptr));
@@ -654,17 +679,6 @@ int compress_device_impl(sccg_ctx* ctx, const sccg_params& P, const uint8_t* rfa
         }
         ~WorkerJoin() { join(); }
     } lines{&ctx->worker};
-    // The walk's R'-only preparation (anchor samples, positions of the target's first k-mer read off
-    // its FASTA) starts on the side stream as soon as R' exists, beside the target's strip.
-    // The walk workspace is sized by the FASTA lengths (>= |R'|, |T'|), so the early sweep needs no
-    // host read of |R'| (it reads it on the device) and the walk reuses the same carve.
-    const size_t wsb = walk_workspace_bytes(rn, tn, kg, walk_chunk(tn));
-    if (rn < INT32_MAX - 8 && tn < INT32_MAX - 8) {
-        HIPTRY(hipStreamWaitEvent(ctx->side, ctx->ev_hdr, 0));
-        void* ws_early = ctx->get(B_WALK, wsb);
-        if (!ws_early) return ctx->fail(SCCG_E_NOMEM, "walk workspace of %zu bytes", wsb);
-        TRY(global_sweep_early(Rp, rn, sc + 8, tfa, tn, sc, kg, mg, walk_chunk(tn), ws_early, wsb, ctx->side));
-    }
     HIPTRY(hipStreamWaitEvent(s, ctx->ev_rstrip, 0));
     // ---- fork.  The local pass (compression.cpp:372-474, main stream) is latency-bound; the
     //      global walk's input-only preparation (side stream) and the header + run lines (side2)

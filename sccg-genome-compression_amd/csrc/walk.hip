@@ -146,7 +146,7 @@ struct WalkPtrs {
                           // [5] frozen count, [6] frozen-scan first hit, [9] void round, [11] carry count,
                           // [12] trapped triggers of the round end, [13] frozen fills of the round end
     int32_t* trig;        // the round end's trapped triggers (RESPEC_MAX_TRIGGERS)
-    int32_t* tflag;       // per chunk: round in which it was a trapped trigger (k_round_pending)
+    int32_t* tflag;       // per chunk: round in which it was a trapped trigger (k_round_close)
     int32_t* fa_j;        // the round end's frozen fills: chunks fa_j+1 .. fa_l literal with P fa_p (scal[13])
     int32_t* fa_l;
     int32_t* fa_p;
@@ -636,7 +636,7 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
             P = uni(P);
             if (lane == 0) KC->guess[j] = P;
         } else {
-            P = uni(KC->guess[j]);   // re-speculation (k_round_respec)
+            P = uni(KC->guess[j]);   // re-speculation (k_round_close)
         }
         if (lane == 0) { KC->usedX[j] = lo_j; KC->usedP[j] = P; }
     } else if (kind == KIND_FIX) {   // result is committed (or discarded) by k_commit
@@ -891,7 +891,7 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
         }
         // carry on only from a fix-up whose commit is certain (k_commit takes it: its predecessor is
         // not listed, and -- by the rule below -- not carried into either), and not where the
-        // frozen scan (frozen end) or the trapped re-speculation (k_round_respec) resolves faster
+        // frozen scan (frozen end) or the trapped re-speculation (k_round_close) resolves faster
         if (kind != KIND_FIX || (j > 0 && uni(KC->lround[j - 1]) == A.round)) return;
         if (converged || !exit_changed || frozen_end || trapped) return;
         const int32_t j1 = j + 1;
@@ -967,7 +967,15 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
 // round.  Discarded chunks stay pending and are re-walked from the corrected entry.  Exactness
 // never depends on this choice -- the loop only ends when every chunk's trajectory was walked from
 // its predecessor's final exit.
-__global__ void k_commit(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const int32_t* __restrict__ nlist_dev) {
+// The frozen list is then put in chunk order by the block that arrives last (sort_list_block below,
+// grid_last_block on scal[14], which k_walk_init zeroes): no launch of its own.
+constexpr int LS_T = 256;   // (a block this small starts beside the other context's walk grid)
+__device__ __forceinline__ void sort_list_block(const WalkPtrs& A, int32_t* __restrict__ list, const int32_t* __restrict__ count,
+                                                uint32_t* __restrict__ bits, int32_t* wsum);
+__global__ __launch_bounds__(LS_T) void k_commit(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist,
+                                                 const int32_t* __restrict__ nlist_dev) {
+    __shared__ int32_t wsum[LS_T / 64 + 1];
+    __shared__ int last;
     if (A.scal[9]) return;   // void pre-queued round
     if (nlist_dev) nlist = *nlist_dev;
     if (blockIdx.x == 0 && threadIdx.x < FROZEN_MAX) A.fy[threadIdx.x] = INT32_MAX;   // for k_frozen_scan
@@ -989,20 +997,19 @@ __global__ void k_commit(WalkPtrs A, const int32_t* __restrict__ list, int32_t n
             atomicOr(&A.fbits[j >> 5], 1u << (j & 31));
         }
     }
+    if (!grid_last_block(reinterpret_cast<unsigned int*>(A.scal + 14), &last)) return;
+    sort_list_block(A, A.flist, A.scal + 5, A.fbits, wsum);
 }
 
 // The round's frozen list and carry list in chunk order (k_commit and k_walk append in atomic
 // order, and mark each entry in a chunk bitmap): which chunks the blind frozen batch (FROZEN_FIRST)
 // and the later batches take, which chunks the CARRY_GRID carry waves take, and so the round's
-// fills and the next pending list, no longer depend on which wave appended first -- the rounds are
-// the same on every run, however long the lists.  One block: the bitmap's words in contiguous
-// shares per thread, a block scan of their popcounts, the list rewritten in chunk order, the words
-// cleared for the next round.
-constexpr int LS_T = 256;   // (a block this small starts beside the other context's walk grid)
-__global__ __launch_bounds__(LS_T) void k_list_sort(WalkPtrs A, int32_t* __restrict__ list, const int32_t* __restrict__ count,
-                                                    uint32_t* __restrict__ bits) {
-    if (A.scal[9]) return;
-    __shared__ int32_t wsum[LS_T / 64 + 1];
+// fills and the next pending list, do not depend on which wave appended first -- the rounds are
+// the same on every run, however long the lists.  One block of LS_T threads: the bitmap's words in
+// contiguous shares per thread, a block scan of their popcounts, the list written in chunk order,
+// the words cleared for the next round.  (wsum: LS_T / 64 + 1 LDS words)
+__device__ __forceinline__ void sort_list_block(const WalkPtrs& A, int32_t* __restrict__ list, const int32_t* __restrict__ count,
+                                                uint32_t* __restrict__ bits, int32_t* wsum) {
     if (*count <= 0) return;   // (nothing appended: no bit set)
     const int32_t nw = (A.C + 31) >> 5;
     const int32_t per = (nw + LS_T - 1) / LS_T, w0 = (int32_t)threadIdx.x * per;
@@ -1025,6 +1032,13 @@ __global__ __launch_bounds__(LS_T) void k_list_sort(WalkPtrs A, int32_t* __restr
         bits[w] = 0;
         for (; b; b &= b - 1) list[at++] = (w << 5) + __ffs((int)b) - 1;
     }
+}
+// (the carry list's sort, a launch of its own ahead of the carry walk)
+__global__ __launch_bounds__(LS_T) void k_list_sort(WalkPtrs A, int32_t* __restrict__ list, const int32_t* __restrict__ count,
+                                                    uint32_t* __restrict__ bits) {
+    __shared__ int32_t wsum[LS_T / 64 + 1];
+    if (A.scal[9]) return;
+    sort_list_block(A, list, count, bits, wsum);
 }
 
 // Frozen chunks (committed fix-ups that ended in a long literal run with P unchanged up to their
@@ -1133,6 +1147,7 @@ __global__ void k_walk_init(WalkPtrs A, int32_t startX, int32_t startP) {
         A.scal[0] = 0; A.scal[1] = 0; A.scal[2] = startX; A.scal[3] = startP;
         A.scal[5] = 0;   // frozen count (k_walk resets it too, but a void round's k_walk returns first)
         A.scal[11] = 0;  // carry list
+        A.scal[14] = 0; A.scal[15] = 0;   // arrival tickets (k_commit, k_round_close), 0 between launches
         A.snapX[0] = startX;
         A.snapP[0] = startP;
     }
@@ -1152,14 +1167,13 @@ __global__ void k_spec_rest(WalkPtrs A) {
     }
 }
 
-// The end of a round, three launches (one block over all chunks was a latency-bound loop of
+// The end of a round, two launches (one block over all chunks was a latency-bound loop of
 // ~70 us per round, the fixed cost the stuck T2T-like pairs pay ~100 times):
-//   k_round_fill     one wave: the frozen fills of a batch; resets the pending list and triggers;
-//   k_round_pending  grid, one thread per chunk: the chunks whose entry state (predecessor's exit)
-//                    differs from the one their trajectory used -> plist, scal[0] (list order is
-//                    free: the walk takes the listed chunks in any order);
-//   k_round_respec   one block: re-speculation after the trapped triggers the scan found.
-constexpr int RESPEC_T = 1024;
+//   k_round_fill   one block: the frozen fills of a batch; resets the pending list and triggers;
+//   k_round_close  grid, one thread per chunk: applies the fills, then lists the chunks whose entry
+//                  state (predecessor's exit) differs from the one their trajectory used -> plist,
+//                  scal[0] (list order is free: the walk takes the listed chunks in any order);
+//                  the block that arrives last re-speculates after the trapped triggers found.
 // (1) one block: the batch's frozen chunks sorted by chunk (rank sort), and the fills of the ones no
 //     earlier fill covers -> fa_j / fa_l / fa_p, count scal[13]; also resets the pending list
 __global__ __launch_bounds__(FROZEN_MAX) void k_round_fill(WalkPtrs A, int fbase, int fcap) {
@@ -1197,75 +1211,96 @@ __global__ __launch_bounds__(FROZEN_MAX) void k_round_fill(WalkPtrs A, int fbase
     }
 }
 
-// (1b) grid, one thread per chunk: apply the fills (ranges disjoint and in chunk order)
-__global__ __launch_bounds__(256) void k_round_fillg(WalkPtrs A) {
-    if (A.scal[9]) return;
+// (2) grid, one thread per chunk.  The fills (ranges disjoint and in chunk order) are applied by
+//     the filled chunk's own thread; its successor's thread needs that chunk's exit in the same
+//     launch, so it derives it from the fill list as well instead of reading it back.  A chunk no
+//     fill covers is written by nobody here, and its state is read as it stands.
+constexpr int RT_T = 256;
+__global__ __launch_bounds__(RT_T) void k_round_close(WalkPtrs A) {
+    if (A.scal[9]) return;   // void pre-queued round
     __shared__ int32_t fj[FROZEN_MAX], fl[FROZEN_MAX], fp[FROZEN_MAX];
+    __shared__ int32_t trig[RESPEC_MAX_TRIGGERS];
+    __shared__ int32_t wsum[RT_T / 64 + 1];
+    __shared__ int last;
     const int na = A.scal[13];
-    if (!na) return;
-    for (int i = (int)threadIdx.x; i < na; i += 256) { fj[i] = A.fa_j[i]; fl[i] = A.fa_l[i]; fp[i] = A.fa_p[i]; }
+    for (int i = (int)threadIdx.x; i < na; i += RT_T) { fj[i] = A.fa_j[i]; fl[i] = A.fa_l[i]; fp[i] = A.fa_p[i]; }
     __syncthreads();
-    const int32_t q = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (q >= A.C) return;
-    int lo = 0, hi = na;   // entries with fj < q
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (fj[mid] < q) lo = mid + 1; else hi = mid;
-    }
-    if (lo == 0 || q > fl[lo - 1]) return;
-    const int32_t P = fp[lo - 1];
-    const int32_t lastk1 = A.nT - A.k + 1;
-    const int32_t lo_q = chunk_lo(A, q), hi_q = chunk_hi(A, q);
-    A.cnt[A.cur[q]][q] = 0;
-    A.usedX[q] = lo_q < lastk1 ? lo_q : lastk1;
-    A.usedP[q] = P;
-    A.exitX[q] = hi_q < lastk1 ? hi_q : lastk1;
-    A.exitP[q] = P;
-    A.changed[q] = 0;
-    A.seedq[q] = 0;
-    A.trapped[q] = 0;
-}
-
-__global__ __launch_bounds__(256) void k_round_pending(WalkPtrs A) {
-    if (A.scal[9]) return;
     const int32_t next = A.round + 1;
+    const int32_t lastk1 = A.nT - A.k + 1;
+    // the fill that covers chunk q (fj < q <= fl), if any -> its P
+    auto filled = [&](int32_t q, int32_t* P) -> bool {
+        int lo = 0, hi = na;   // entries with fj < q
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (fj[mid] < q) lo = mid + 1; else hi = mid;
+        }
+        if (lo == 0 || q > fl[lo - 1]) return false;
+        *P = fp[lo - 1];
+        return true;
+    };
     const int32_t j = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (j >= A.C) return;
-    const int32_t ex = j ? A.exitX[j - 1] : A.scal[2];
-    const int32_t ep = j ? A.exitP[j - 1] : A.scal[3];
-    const int32_t ux = A.usedX[j], up = A.usedP[j], lr = A.lround[j];
-    const bool pend = ex != INVALID && !(ex == ux && ep == up);
-    if (!pend) {
-        if (lr == next) A.lround[j] = A.round;   // listed by an earlier batch of this round
-        // (a chunk without a trajectory after its first speculation -- no anchor vote anywhere in
-        // it -- waits until its predecessor settles)
-        return;
+    if (j < A.C) {
+        int32_t ux, up, P = 0;
+        if (na && filled(j, &P)) {
+            const int32_t lo_j = chunk_lo(A, j), hi_j = chunk_hi(A, j);
+            ux = lo_j < lastk1 ? lo_j : lastk1;
+            up = P;
+            A.cnt[A.cur[j]][j] = 0;
+            A.usedX[j] = ux;
+            A.usedP[j] = up;
+            A.exitX[j] = hi_j < lastk1 ? hi_j : lastk1;
+            A.exitP[j] = P;
+            A.changed[j] = 0;
+            A.seedq[j] = 0;
+            A.trapped[j] = 0;
+        } else {
+            ux = A.usedX[j];
+            up = A.usedP[j];
+        }
+        // the entry state: the predecessor's exit after the fills
+        int32_t ex, ep;
+        bool pred_trapped = false;
+        if (j == 0) {
+            ex = A.scal[2];
+            ep = A.scal[3];
+        } else if (na && filled(j - 1, &P)) {
+            const int32_t hi_p = chunk_hi(A, j - 1);
+            ex = hi_p < lastk1 ? hi_p : lastk1;
+            ep = P;
+        } else {
+            ex = A.exitX[j - 1];
+            ep = A.exitP[j - 1];
+            pred_trapped = A.trapped[j - 1] != 0;
+        }
+        const int32_t lr = A.lround[j];
+        const bool pend = ex != INVALID && !(ex == ux && ep == up);
+        if (!pend) {
+            if (lr == next) A.lround[j] = A.round;   // listed by an earlier batch of this round
+            // (a chunk without a trajectory after its first speculation -- no anchor vote anywhere in
+            // it -- waits until its predecessor settles)
+        } else {
+            A.snapX[j] = ex;
+            A.snapP[j] = ep;
+            A.kind[j] = KIND_FIX;
+            A.lround[j] = next;
+            A.plist[atomicAdd(&A.scal[0], 1)] = j;
+            // (the re-speculation takes the first RESPEC_MAX_TRIGGERS in chunk order; a chunk that was a
+            // trigger in an earlier pending pass of this round -- before a chain filled its predecessor --
+            // and is not one now is cleared)
+            const bool tr = pred_trapped && A.walked[j - 1] == A.round;
+            A.tflag[j] = tr ? A.round : -1;
+            if (tr) atomicAdd(&A.scal[12], 1);
+        }
     }
-    A.snapX[j] = ex;
-    A.snapP[j] = ep;
-    A.kind[j] = KIND_FIX;
-    A.lround[j] = next;
-    A.plist[atomicAdd(&A.scal[0], 1)] = j;
-    // (k_round_respec takes the first RESPEC_MAX_TRIGGERS in chunk order; a chunk that was a trigger
-    // in an earlier pending pass of this round -- before a chain filled its predecessor -- and is
-    // not one now is cleared)
-    const bool trig = j > 0 && A.trapped[j - 1] && A.walked[j - 1] == A.round;
-    A.tflag[j] = trig ? A.round : -1;
-    if (trig) atomicAdd(&A.scal[12], 1);
-}
+    if (!grid_last_block(reinterpret_cast<unsigned int*>(A.scal + 15), &last)) return;
 
-// re-speculate the still-speculative chunks after each trapped trigger (see TRAP_P)
-__global__ __launch_bounds__(RESPEC_T) void k_round_respec(WalkPtrs A) {
-    if (A.scal[9]) return;
+    // re-speculate the still-speculative chunks after each trapped trigger (see TRAP_P)
     const int ntrig = A.scal[12];
     if (!ntrig) return;
-    const int32_t next = A.round + 1;
-    __shared__ int32_t trig[RESPEC_MAX_TRIGGERS];
-    __shared__ int32_t wsum[RESPEC_T / 64 + 1];
     // the round's triggers in chunk order (the first RESPEC_MAX_TRIGGERS): thread t takes a contiguous
     // share of the chunks, a block scan of the shares' counts places them -- the same set every run
     {
-        const int32_t per = (A.C + RESPEC_T - 1) / RESPEC_T, c0 = (int32_t)threadIdx.x * per;
+        const int32_t per = (A.C + RT_T - 1) / RT_T, c0 = (int32_t)threadIdx.x * per;
         int cnt = 0;
         // (a trigger must still be pending: a later frozen batch of the same round may have filled it,
         // and a stale trigger's run would overlap an earlier trigger's -- two waves writing different
@@ -1277,8 +1312,8 @@ __global__ __launch_bounds__(RESPEC_T) void k_round_respec(WalkPtrs A) {
         __syncthreads();
         if (threadIdx.x == 0) {
             int run = 0;
-            for (int i = 0; i < RESPEC_T / 64; i++) { const int x = wsum[i]; wsum[i] = run; run += x; }
-            wsum[RESPEC_T / 64] = run;
+            for (int i = 0; i < RT_T / 64; i++) { const int x = wsum[i]; wsum[i] = run; run += x; }
+            wsum[RT_T / 64] = run;
         }
         __syncthreads();
         int at = wsum[w] + incl - cnt;
@@ -1286,15 +1321,15 @@ __global__ __launch_bounds__(RESPEC_T) void k_round_respec(WalkPtrs A) {
             if (A.tflag[q] == A.round && A.lround[q] == next) trig[at++] = q;
         __syncthreads();
     }
-    const int nt = wsum[RESPEC_T / 64] < RESPEC_MAX_TRIGGERS ? wsum[RESPEC_T / 64] : RESPEC_MAX_TRIGGERS;
+    const int nt = wsum[RT_T / 64] < RESPEC_MAX_TRIGGERS ? wsum[RT_T / 64] : RESPEC_MAX_TRIGGERS;
     const int w = (int)(threadIdx.x >> 6), nw = (int)(blockDim.x >> 6), lane = lane_id();
     for (int t = w; t < nt; t += nw) {
-        const int32_t j = trig[t], P = A.snapP[j];
-        for (int32_t q0 = j + 1; q0 <= j + RESPEC_AHEAD && q0 < A.C; q0 += 64) {
+        const int32_t jt = trig[t], P = A.snapP[jt];
+        for (int32_t q0 = jt + 1; q0 <= jt + RESPEC_AHEAD && q0 < A.C; q0 += 64) {
             const int32_t q = q0 + lane;
             // every chunk after a pending one is unconfirmed, so replacing its trajectory by another
             // guess never discards settled work; the run stops at the next pending chunk
-            const bool ok = q < A.C && q <= j + RESPEC_AHEAD && A.lround[q] != next;
+            const bool ok = q < A.C && q <= jt + RESPEC_AHEAD && A.lround[q] != next;
             const unsigned long long okm = __ballot(ok);
             const unsigned long long run = ~okm ? okm & ((1ull << first_lane(~okm)) - 1) : okm;   // up to the first stop
             if ((run >> lane) & 1ull) {
@@ -1308,12 +1343,10 @@ __global__ __launch_bounds__(RESPEC_T) void k_round_respec(WalkPtrs A) {
     }
 }
 
-// the three round-end launches (fcap = 0: the pending scan alone)
+// the two round-end launches (fcap = 0: no fills, the pending scan alone)
 int launch_round_end(const WalkPtrs& A, int fbase, int fcap, hipStream_t s) {
     hipLaunchKernelGGL(k_round_fill, dim3(1), dim3(FROZEN_MAX), 0, s, A, fbase, fcap);
-    if (fcap > 0) hipLaunchKernelGGL(k_round_fillg, dim3(grid_for(A.C, 256)), dim3(256), 0, s, A);
-    hipLaunchKernelGGL(k_round_pending, dim3(grid_for(A.C, 256)), dim3(256), 0, s, A);
-    hipLaunchKernelGGL(k_round_respec, dim3(1), dim3(RESPEC_T), 0, s, A);
+    hipLaunchKernelGGL(k_round_close, dim3(grid_for(A.C, RT_T)), dim3(RT_T), 0, s, A);
     SCCG_HIP(hipGetLastError());
     return 0;
 }
@@ -2143,8 +2176,10 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_sweep_early(WalkPtrs A) {
 
 // after T' exists: statistics of x0 = 0 over the early sweep's positions (as k_key0 +
 // k_cand_reduce would leave them in fc[4..11]).  Grid-wide: every wave extends one position at a
-// time (wave_lce: 2 KiB per round trip), per-block results go to fcb and k_cand_stats_fin merges
-// them -- a repeat-rich first k-mer (hundreds of positions) no longer serialises on one block.
+// time (wave_lce: 2 KiB per round trip), per-block results go to fcb and the block that arrives
+// last merges them -- a repeat-rich first k-mer (hundreds of positions) no longer serialises on
+// one block, and the merge is no launch of its own.  The arrival ticket is fc[14]: zero before the
+// launch (global_sweep_early sets it), and the last block leaves it zero.
 constexpr int CAND_STATS_GRID = 256;
 // whole wave (one round trip: lane i compares byte i of the FASTA-read k-mer with T')
 __device__ __forceinline__ bool cand_stats_usable(const WalkPtrs& A) {
@@ -2156,7 +2191,7 @@ __device__ __forceinline__ bool cand_stats_usable(const WalkPtrs& A) {
 }
 __global__ __launch_bounds__(SCCG_BLOCK) void k_cand_stats(WalkPtrs A) {
     __shared__ CandBest wbest[SCCG_BLOCK / 64];
-    __shared__ int ok;
+    __shared__ int ok, last;
     const int k = A.k;
     const unsigned long long cnt = A.fc[13];
     if (threadIdx.x < 64) {
@@ -2184,19 +2219,12 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_cand_stats(WalkPtrs A) {
         unsigned long long* o = A.fcb + 4 * blockIdx.x;
         o[0] = v.l; o[1] = v.cnt; o[2] = v.has0; o[3] = v.minkey;
     }
-}
-
-__global__ __launch_bounds__(1024) void k_cand_stats_fin(WalkPtrs A, int nblk) {
-    __shared__ CandBest wbest[16];
-    __shared__ int ok;
-    if (threadIdx.x < 64) {
-        const bool u = cand_stats_usable(A);
-        if (threadIdx.x == 0) { ok = u; A.fc[12] = u ? 1 : 2; }
-    }
-    __syncthreads();
+    if (!grid_last_block(reinterpret_cast<unsigned int*>(A.fc + 14), &last)) return;
+    if (threadIdx.x == 0) A.fc[12] = ok ? 1 : 2;
     if (!ok) return;
-    CandBest v{0, 0, 0, ~0ull};
-    for (int b = (int)threadIdx.x; b < nblk; b += (int)blockDim.x) {
+    // every block's statistics are in fcb: merge them (as k_cand_reduce does for the full sweep)
+    v = CandBest{0, 0, 0, ~0ull};
+    for (int b = (int)threadIdx.x; b < (int)gridDim.x; b += SCCG_BLOCK) {
         const unsigned long long* o = A.fcb + 4 * b;
         v = cb_merge(v, CandBest{(uint32_t)o[0], (uint32_t)o[1], (uint32_t)o[2], o[3]});
     }
@@ -2204,7 +2232,7 @@ __global__ __launch_bounds__(1024) void k_cand_stats_fin(WalkPtrs A, int nblk) {
     if (lane_id() == 0) wbest[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int i = 1; i < (int)(blockDim.x >> 6); i++) v = cb_merge(v, wbest[i]);
+        for (int i = 1; i < SCCG_BLOCK / 64; i++) v = cb_merge(v, wbest[i]);
         A.fc[8] = v.l; A.fc[9] = v.cnt; A.fc[10] = v.has0; A.fc[11] = v.minkey;
         A.fc[4] = v.cnt ? 0ull : ~0ull;
         A.fc[5] = ~0ull;
@@ -2905,7 +2933,8 @@ WalkPtrs make_ptrs(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nT
 void global_prepare_reset() { g_prep = Prepared{}; g_early = Early{}; }
 
 int global_sweep_early(const uint8_t* Rp, int64_t nRp, const int64_t* d_nRp, const uint8_t* tgt_fa, int64_t tn,
-                       const int64_t* d_hdr, int k, int m, int chunk, void* ws, size_t ws_bytes, hipStream_t s) {
+                       const int64_t* d_hdr, int k, int m, int chunk, void* ws, size_t ws_bytes, hipStream_t s_head,
+                       hipEvent_t ev_head, hipStream_t s) {
     g_early = Early{};
     if (m < 0 || 2 * m + 1 > WCAP || k > KMAX || k < 1) return SCCG_E_UNSUPPORTED;
     if (nRp < k || tn <= 0) return 0;   // no walk can use it
@@ -2915,9 +2944,13 @@ int global_sweep_early(const uint8_t* Rp, int64_t nRp, const int64_t* d_nRp, con
     WalkPtrs A = make_ptrs(Rp, nRp, nullptr, tn, k, m, chunk, ws, ws_bytes, &used);
     if (used > ws_bytes) return SCCG_E_INTERNAL;
     A.dnR = d_nRp;
-    RC(anchor_generation(A, ws, s));
-    RC(set_u64(A.fc + 12, {0, 0}, s));
-    hipLaunchKernelGGL(k_first_kmer, dim3(1), dim3(SCCG_BLOCK), 0, s, tgt_fa, tn, d_hdr, k, (int64_t)1 << 20, A.kb);
+    // fc[12..13], and k_cand_stats' ticket fc[14] (its last block leaves it 0 again; the workspace
+    // may be new)
+    RC(anchor_generation(A, ws, s_head));
+    RC(set_u64(A.fc + 12, {0, 0, 0}, s_head));
+    hipLaunchKernelGGL(k_first_kmer, dim3(1), dim3(SCCG_BLOCK), 0, s_head, tgt_fa, tn, d_hdr, k, (int64_t)1 << 20, A.kb);
+    SCCG_HIP(hipEventRecord(ev_head, s_head));
+    SCCG_HIP(hipStreamWaitEvent(s, ev_head, 0));
     PROF_LAUNCH(PROF_ANCHOR, s, k_sweep_early, dim3(first_sweep_grid(A)), dim3(SCCG_BLOCK), 0, s, A);
     SCCG_HIP(hipGetLastError());
     g_early = Early{ws, Rp, nRp, k, A.agen, A.abits};
@@ -2939,7 +2972,6 @@ int global_prepare(const uint8_t* Rp, int64_t nRp, const uint8_t* Tp, int64_t nT
         A.agen = e.agen;
         if (A.nR >= A.k && A.nT >= A.k) {
             hipLaunchKernelGGL(k_cand_stats, dim3(CAND_STATS_GRID), dim3(SCCG_BLOCK), 0, s, A);
-            hipLaunchKernelGGL(k_cand_stats_fin, dim3(1), dim3(1024), 0, s, A, CAND_STATS_GRID);
             SCCG_HIP(hipGetLastError());
         }
     } else {
@@ -3023,7 +3055,6 @@ int WalkRun::queue_round(int fbase_cap, bool dev_nlist) {
     if (dev_nlist) RC(launch_carry(A, s));
     hipLaunchKernelGGL(k_commit, dim3(grid_for(A.C, 256) > 4096 ? 4096 : grid_for(A.C, 256)), dim3(256), 0, s, A,
                        (const int32_t*)A.plist, A.C, nd);
-    hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
     if (fbase_cap > 0) hipLaunchKernelGGL(k_frozen_scan, dim3(FZ_GRID, fbase_cap), dim3(FZ_T), 0, s, A, 0);
     SCCG_HIP(hipGetLastError());
     RC(launch_round_end(A, 0, fbase_cap, s));
@@ -3204,7 +3235,6 @@ int WalkRun::run_rounds(bool frozen_first) {
             // handled after the round's sync.
             hipLaunchKernelGGL(k_commit, dim3(grid_for(nlist, 256) > 4096 ? 4096 : grid_for(nlist, 256)), dim3(256), 0, s, A,
                                (const int32_t*)A.plist, nlist, (const int32_t*)nullptr);
-            hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
         }
         res->rounds = round;
         int32_t rs[6];
@@ -3267,7 +3297,6 @@ int WalkRun::run_rounds(bool frozen_first) {
                 RC(dev_set_i32(A.scal + 5, 1, {0}, s));   // frozen list of the resumed chunks
                 hipLaunchKernelGGL(k_commit, dim3(grid_for(nr, 256) > 4096 ? 4096 : grid_for(nr, 256)), dim3(256), 0, s, A,
                                    (const int32_t*)A.rlist, nr, (const int32_t*)nullptr);
-                hipLaunchKernelGGL(k_list_sort, dim3(1), dim3(LS_T), 0, s, A, A.flist, (const int32_t*)(A.scal + 5), A.fbits);
                 SCCG_HIP(hipGetLastError());
             }
             {
