@@ -277,7 +277,38 @@ int sccg_reader_fetch_device(sccg_reader* reader, const sccg_region* regions /*h
 #define SCCG_FETCH_REVCOMP 2u   /* every region on the reverse strand */
 typedef struct { uint32_t encoding, dtype, flags, reserved /* 0 */; } sccg_fetch_format;
 
-size_t sccg_fetch_bytes_per_base(const sccg_fetch_format* fmt);   /* 1, 1, 4, 8, 8, 16; 0 = invalid format */
+/* Origin fetch: where each base comes from.  The format {SCCG_ENC_ORIGIN, SCCG_DT_I32, flags, 0} is taken
+ * by sccg_reader_fetch_encoded[_device] and sccg_cohort_fetch[_device]; a base is one little-endian int32:
+ *
+ *   r >= 0   a token copied the base from position r of the reference sequence R -- the reference
+ *            file's non-header lines joined, whitespace removed (decompression.cpp:53-58), 0-based; for
+ *            a one-record FASTA r + 1 is the samtools faidx coordinate.  NOT a position of R' (the
+ *            N-erased string the tokens index, decompression.cpp:105-110): the library maps it back.
+ *   -1       a literal: the base is carried by the record line itself
+ *   -2       a base of one of the target's N runs (inserted from the N line, decompression.cpp:241-249;
+ *            it is in neither R' nor the record line)
+ *
+ * Layout, the region rules (empty, repeated, overlapping, unordered, n == 0), the size query and
+ * SCCG_E_NOMEM with the bytes needed are the encoded fetch's, at 4 bytes per base; d_out must be 4-byte
+ * aligned (else SCCG_E_INVALID); one copy of the region list and one kernel launch per call.  Output
+ * base q of a reversed region is position end - 1 - q and its value is that position's origin,
+ * unchanged: a reference position is not complemented.  The encoding is case-blind: SCCG_FETCH_UPPER
+ * is accepted and ignored and the lowercase runs are never read.  Every other dtype with ORIGIN, and
+ * I32 with any other encoding, is SCCG_E_INVALID.
+ *
+ * Which readers have reference coordinates (sccg_reader_has_coords): one whose record's N line is ","
+ * always (R' is R position for position), private or shared; one whose record indexes the erased
+ * form only when it was opened through a sccg_reference whose `forms` carried SCCG_REF_COORDS, which
+ * keeps the R' -> R map (below).  An ORIGIN fetch on a reader without them returns SCCG_E_UNSUPPORTED
+ * -- the size query too; nothing is written; sccg_last_error says which.  In a cohort, bad regions
+ * (SCCG_E_INVALID) and regions of samples without coordinates (SCCG_E_UNSUPPORTED) are found in one
+ * pass: the first offending region in list order decides the status and is named.  Format errors come
+ * first; the coordinate check is made for ORIGIN only. */
+#define SCCG_ENC_ORIGIN 3u   /* where each base comes from; dtype must be SCCG_DT_I32 */
+#define SCCG_DT_I32     4u   /* valid with SCCG_ENC_ORIGIN only */
+int sccg_reader_has_coords(const sccg_reader* reader);   /* 1 / 0; 0 for NULL */
+
+size_t sccg_fetch_bytes_per_base(const sccg_fetch_format* fmt);   /* 1, 1, 4, 8, 8, 16; ORIGIN 4; 0 = invalid format */
 int sccg_reader_fetch_encoded(sccg_reader* reader, const sccg_region* regions, size_t n, const uint8_t* strand,
                               const sccg_fetch_format* fmt, sccg_buf* out);
 int sccg_reader_fetch_encoded_device(sccg_reader* reader, const sccg_region* regions /*host*/, size_t n,
@@ -307,10 +338,19 @@ int sccg_reader_fetch_encoded_device(sccg_reader* reader, const sccg_region* reg
  * open through it), and the memory goes with the last reader's sccg_reader_close.  All of that
  * happens before sccg_ctx_destroy.  sccg_reader_device_bytes is the reader's own persistent
  * allocation (for a private reader R' included; the staging a fetch grows is not counted); 0 for NULL.
- * The _device forms take device pointers and a hipStream_t (NULL = the context's own stream). */
+ * The _device forms take device pointers and a hipStream_t (NULL = the context's own stream).
+ *
+ * `forms` is a mask of forms plus one option, SCCG_REF_COORDS: also keep the R' -> R map the origin
+ * fetch needs for the erased form -- the maximal runs of uppercase 'N' in R (a lowercase 'n' is not
+ * erased), found on the device at open; 16 bytes per run, counted by sccg_reference_device_bytes.
+ * SCCG_REF_COORDS alone is both forms plus the map; with form bits, those forms plus the map (with
+ * SCCG_REF_KEPT alone the map is empty: the kept form needs none).  Without the bit every allocation
+ * and sccg_reference_device_bytes are what they are without this option.  Any other bit is
+ * SCCG_E_INVALID; a reference of 2^31 - 1 bases or more cannot carry the map (SCCG_E_UNSUPPORTED). */
 typedef struct sccg_reference sccg_reference;
 #define SCCG_REF_ERASED 1u   /* R' as a record with an N-run line needs it (N erased, decompression.cpp:105-110) */
 #define SCCG_REF_KEPT   2u   /* R' as a record whose N line is "," needs it (N kept) */
+#define SCCG_REF_COORDS 4u   /* option: keep the R' -> R map (reference coordinates for SCCG_ENC_ORIGIN) */
 int sccg_reference_open(sccg_ctx* ctx, const char* ref_fa, size_t ref_len, uint32_t forms /*0 = both*/, sccg_reference** out);
 int sccg_reference_open_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_len, uint32_t forms, sccg_reference** out,
                                void* stream);

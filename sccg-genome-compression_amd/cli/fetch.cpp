@@ -7,7 +7,15 @@
 // --reverse-complement; recognised as the first argument only) prints every region reverse-
 // complemented, as `samtools faidx -i` does, with `/rc` appended to its header line.  Exit code 1 on
 // usage / region / open / format errors; the regions are parsed before the GPU is touched.
+// `fetch --origin <record_file> <reference_file> <region>...` (first argument only) prints, per
+// region, the usual header line and then where its bases come from (SCCG_ENC_ORIGIN, through a
+// reference opened with SCCG_REF_COORDS): one tab-separated line per maximal run, everything 1-based
+// and inclusive -- `tbegin tend rbegin rend` for bases copied from consecutively ascending reference
+// positions, `tbegin tend *` for literals of the record line, `tbegin tend N` for bases of the target's
+// N runs.  --origin together with -i is a usage error.
 #include "cli_common.h"
+
+#include <cstring>
 
 // decimal digits only, no sign, fits int64
 static bool parse_pos(const std::string& s, int64_t* v) {
@@ -23,11 +31,16 @@ static bool parse_pos(const std::string& s, int64_t* v) {
 
 int main(int argc, char* argv[]) {
     const bool rc_flag = argc > 1 && (std::string(argv[1]) == "-i" || std::string(argv[1]) == "--reverse-complement");
-    const int a0 = rc_flag ? 2 : 1;   // the first file argument
-    if (argc < a0 + 3) {
-        std::cerr << "Usage: " << argv[0] << " [-i] <record_file> <reference_file> <region>...\n"
+    const bool origin = argc > 1 && std::string(argv[1]) == "--origin";
+    const int a0 = rc_flag || origin ? 2 : 1;   // the first file argument
+    const bool both = argc > 2 && ((origin && (std::string(argv[2]) == "-i" || std::string(argv[2]) == "--reverse-complement")) ||
+                                   (rc_flag && std::string(argv[2]) == "--origin"));
+    if (argc < a0 + 3 || both) {
+        std::cerr << "Usage: " << argv[0] << " [-i | --origin] <record_file> <reference_file> <region>...\n"
                   << "  region: begin-end (1-based, inclusive) or pos\n"
-                  << "  -i, --reverse-complement (first argument only): every region reverse-complemented\n";
+                  << "  -i, --reverse-complement (first argument only): every region reverse-complemented\n"
+                  << "  --origin (first argument only, not with -i): where each base comes from, one line per run:\n"
+                  << "      tbegin tend rbegin rend (copied from the reference) | tbegin tend * (literal) | tbegin tend N\n";
         return 1;
     }
     const std::string rec_path = argv[a0], ref_path = argv[a0 + 1];
@@ -60,14 +73,24 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     sccg_reader* rd = nullptr;
-    rc = sccg_reader_open(ctx, ref.data(), ref.size(), rec.data(), rec.size(), &rd);
+    if (origin) {   // through a reference that keeps the R' -> R map; the reader holds it from here on
+        sccg_reference* rf = nullptr;
+        rc = sccg_reference_open(ctx, ref.data(), ref.size(), SCCG_REF_COORDS, &rf);
+        if (!rc) rc = sccg_reader_open_shared(rf, rec.data(), rec.size(), &rd);
+        sccg_reference_close(rf);
+    } else {
+        rc = sccg_reader_open(ctx, ref.data(), ref.size(), rec.data(), rec.size(), &rd);
+    }
     if (rc) {
         std::cerr << "Error opening the record: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
         sccg_ctx_destroy(ctx);
         return 1;
     }
     sccg_buf seq{};
-    if (rc_flag) {
+    if (origin) {
+        const sccg_fetch_format fmt{SCCG_ENC_ORIGIN, SCCG_DT_I32, 0, 0};
+        rc = sccg_reader_fetch_encoded(rd, regions.data(), regions.size(), nullptr, &fmt, &seq);
+    } else if (rc_flag) {
         const sccg_fetch_format fmt{SCCG_ENC_ASCII, SCCG_DT_U8, SCCG_FETCH_REVCOMP, 0};
         rc = sccg_reader_fetch_encoded(rd, regions.data(), regions.size(), nullptr, &fmt, &seq);
     } else {
@@ -87,6 +110,22 @@ int main(int argc, char* argv[]) {
     for (const sccg_region& r : regions) {
         out += ">" + name + ":" + std::to_string(r.begin + 1) + "-" + std::to_string(r.end) + (rc_flag ? "/rc\n" : "\n");
         const size_t len = (size_t)(r.end - r.begin);
+        if (origin) {   // maximal runs: ascending reference positions, literals, N
+            const char* o4 = seq.data + 4 * at;
+            auto val = [o4](size_t k) { int32_t v; memcpy(&v, o4 + 4 * k, 4); return v; };
+            for (size_t k = 0; k < len;) {
+                const int32_t v = val(k);
+                size_t e = k + 1;
+                while (e < len && (v >= 0 ? val(e) == v + (int32_t)(e - k) : val(e) == v)) e++;
+                out += std::to_string(r.begin + 1 + (int64_t)k) + "\t" + std::to_string(r.begin + (int64_t)e) + "\t";
+                if (v >= 0) out += std::to_string((int64_t)v + 1) + "\t" + std::to_string((int64_t)v + (int64_t)(e - k));
+                else out += v == -1 ? "*" : "N";
+                out += '\n';
+                k = e;
+            }
+            at += len;
+            continue;
+        }
         for (size_t k = 0; k < len; k += 50) {
             out.append(seq.data + at + k, len - k < 50 ? len - k : 50);
             out += '\n';

@@ -61,6 +61,8 @@ int dc_format(const uint8_t* d_dec, int64_t nres, const DcRuns& nr, const DcRuns
 // What a region fetch reads (a reader's own copies, sccg_api.cpp): the record line and its 64-byte
 // block index (state, decoded offset, running p: dc_decode_prepare's d_lp, d_off, d_dsum), R' and
 // both run lists (cum: the N runs' only).  Byte buffers carry the usual readable slack.
+// rm (the origin fetch alone): the runs of 'N' in the reference sequence R that R' has erased -- R'
+// position v is R position v + (len of every run with start - cum <= v); rm.n == 0: R' is R.
 struct DcFetchSrc {
     const uint8_t* rec;
     int64_t nrec;
@@ -69,6 +71,7 @@ struct DcFetchSrc {
     const int64_t* bdsum;
     const uint8_t* R;
     DcRuns nr, lr;
+    DcRuns rm;
 };
 // d_out[0, F) = the sequence bytes of regions [d_beg[i], d_beg[i] + d_pre[i + 1] - d_pre[i]), i < nreg,
 // concatenated (d_pre: exclusive prefix of the lengths, d_pre[nreg] = F); upper: no lowercase runs.
@@ -92,3 +95,23 @@ struct DcCohortEntry {
 // validated by the caller, as the regions are).  One launch, under the same profiler family.
 int dc_fetch_cohort(const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg, const int32_t* d_samp, int64_t nreg,
                     int64_t F, int enc, int dt, bool upper, bool all_rev, uint8_t* d_out, hipStream_t s);
+
+// Origin fetch (SCCG_ENC_ORIGIN): d_out[0, F) int32, one per base of the same flat space -- the
+// position in the reference sequence a token copied the base from (R' positions through S.rm), -1 for
+// a literal, -2 inside one of the target's N runs; a reversed region's values come in reverse order,
+// unchanged.  src given: the reader's source (d_tab, d_samp unused); src null: region i reads
+// d_tab[d_samp[i]].  d_out 4-byte aligned.  One launch, under the fetch profiler family; R' is not read.
+int dc_fetch_origin(const DcFetchSrc* src, const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg,
+                    const int32_t* d_samp, int64_t nreg, int64_t F, bool all_rev, int32_t* d_out, hipStream_t s);
+
+// The R' -> R map: the maximal runs of the byte 'N' in the stripped, original-case reference d_R[0, n)
+// (n < 2^31, 16-byte aligned, 16 readable bytes behind it).  dc_refmap_count: d_nruns[0] = the runs
+// (d_nruns[1] the same), d_os / d_oe the tiles' ranks for the write (d_cs, d_ce, d_os, d_oe: dc_refmap_tiles(n)
+// entries each; d_partial: 2 * scan_partials_needed(tiles)).  dc_refmap_write: m's arrays (m->n runs, as
+// counted) filled -- start, len, cum -- and *d_total = the N in all of them (d_partial:
+// scan_partials_needed(m->n)).  No host wait in either.
+int64_t dc_refmap_tiles(int64_t n);
+int dc_refmap_count(const uint8_t* d_R, int64_t n, int64_t* d_cs, int64_t* d_ce, int64_t* d_os, int64_t* d_oe, int64_t* d_nruns,
+                    int64_t* d_partial, hipStream_t s);
+int dc_refmap_write(const uint8_t* d_R, int64_t n, const int64_t* d_os, const int64_t* d_oe, DcRuns* m, int64_t* d_total,
+                    int64_t* d_partial, hipStream_t s);

@@ -965,7 +965,81 @@ __device__ __forceinline__ int64_t wave_first(int64_t a, int64_t b, P&& pred) {
 struct FetchSpan {
     int64_t rn0, d0;
 };
-__device__ __forceinline__ FetchSpan fetch_decode_span(const DcFetchSrc& S, int64_t j0, int64_t j1, uint8_t* sdec, uint8_t* st) {
+// The ORIGIN arm keeps where a byte comes from instead of the byte: its tile is FO_TILE int32, decoded
+// offset d at org[opad(d - d0)] -- a literal -1, byte (a - oj) + k of the token at R' position pj the
+// position in the reference sequence R of R' position v = pj + (a - oj) + k.  R' is not read.  (opad:
+// a lane's 16 consecutive entries start 17 words after its neighbour's, so the per-lane walks of the
+// epilogue meet no LDS bank twice.)
+// R' -> R: S.rm lists the runs of 'N' in R that R' has erased; run m is crossed from R' position
+// key(m) = start[m] - cum[m] on, the keys ascend strictly, and v lies at v + (the N of every run with
+// key <= v).  The search is the wave's, once per token piece and not per base: a 64-ary wave_first
+// for the piece's first position v0 gives the bracket [lo, hi) of keys around it and the N count
+// `add` that holds inside; a piece that ends inside the bracket -- nearly every one: a piece is at most
+// 1,024 bases, a reference's runs are far apart -- is v0 + k + add for all its lanes.  The bracket is
+// kept (MapCur, wave-uniform) across tokens and spans of one map: the tokens of a span are neighbours
+// on the reference, so the next one usually loads nothing of the map.  A piece that crosses runs
+// bounds them with a second wave_first and each lane searches those few for its positions.
+constexpr int FO_TILE = FT_W + FT_W / 16;
+__device__ __forceinline__ int opad(int i) { return i + (i >> 4); }
+struct MapCur {
+    int64_t mi, lo, hi, add;   // keys [lo, hi) = [key(mi - 1), key(mi)): add N lie before such a position
+};
+__device__ __forceinline__ int64_t map_key(const DcRuns& M, int64_t m) { return (int64_t)M.start[m] - M.cum[m]; }
+// The bracket around R' position v: wave_first's 64-ary narrowing over the keys, whose last step has
+// the bracket's own entries in the lanes -- key and cum of up to 64 candidates, the upper bound
+// included, loaded in one round and handed over by readlane -- so a map of up to 63 runs (a
+// chromosome's) costs one round of loads, where a search and then a read of its result cost two.
+__device__ __forceinline__ void map_seek(const DcRuns& M, int64_t v, MapCur& c) {
+    const int lane = lane_id();
+    int64_t a = 0, b = M.n;   // the first m with key(m) > v is in [a, b]; key(b) > v, or b == M.n
+    while (b - a > 63) {
+        const int64_t step = (b - a + 63) >> 6;
+        const int64_t m = a + (int64_t)lane * step + step - 1;   // the last entry of this lane's chunk
+        const unsigned long long t = __ballot(m >= b || map_key(M, m) > v);
+        if (!t) { a = b; break; }
+        const int h = __ffsll((long long)t) - 1;
+        const int64_t mh = a + (int64_t)h * step + step - 1;
+        a += (int64_t)h * step;
+        b = mh < b ? mh : b;
+    }
+    const int64_t m = a + lane;   // lanes 0 .. b - a hold entries a .. b
+    const bool in = m <= b && m < M.n;
+    const int64_t cu = in ? M.cum[m] : M.total, ky = in ? (int64_t)M.start[m] - cu : INT64_MAX;
+    const int h = __ffsll((long long)__ballot(m <= b && ky > v)) - 1;   // (lane b - a always qualifies)
+    c.mi = a + h;
+    c.hi = readlane64(ky, h);
+    c.add = readlane64(cu, h);
+    c.lo = h > 0 ? readlane64(ky, h - 1) : c.mi > 0 ? map_key(M, c.mi - 1) : INT64_MIN;
+}
+// org[opad(at + k)] = the R position of R' position v0 + k, k < cnt (the whole wave calls it)
+__device__ __forceinline__ void origin_piece(const DcRuns& M, int64_t v0, int cnt, int32_t* org, int at, MapCur& c) {
+    const int lane = lane_id();
+    if (!M.n) {   // R' is R
+        for (int k = lane; k < cnt; k += 64) org[opad(at + k)] = (int32_t)(v0 + k);
+        return;
+    }
+    if (v0 < c.lo || v0 >= c.hi) map_seek(M, v0, c);
+    if (v0 + cnt <= c.hi) {
+        const int32_t r0 = (int32_t)(v0 + c.add);
+        for (int k = lane; k < cnt; k += 64) org[opad(at + k)] = r0 + k;
+        return;
+    }
+    // runs [c.mi, m1) are crossed inside the piece
+    const int64_t vend = v0 + cnt, m1 = wave_first(c.mi + 1, M.n, [&](int64_t m) { return map_key(M, m) >= vend; });
+    for (int k = lane; k < cnt; k += 64) {
+        const int64_t v = v0 + k;
+        int64_t a = c.mi, b = m1;   // first m with key(m) > v
+        while (a < b) {
+            const int64_t m = (a + b) >> 1;
+            if (map_key(M, m) > v) b = m; else a = m + 1;
+        }
+        org[opad(at + k)] = (int32_t)(v + (a < M.n ? M.cum[a] : M.total));
+    }
+}
+template <bool ORIGIN = false>
+__device__ __forceinline__ FetchSpan fetch_decode_span(const DcFetchSrc& S, int64_t j0, int64_t j1, uint8_t* sdec, uint8_t* st,
+                                                       MapCur* mc = nullptr) {
+    int32_t* org = reinterpret_cast<int32_t*>(sdec);   // (ORIGIN: the tile is the wave's int32 one)
     const int lane = lane_id();
     const uint8_t* __restrict__ rec = S.rec;
     const int64_t n = S.nrec, nblk = (n + TK_B - 1) / TK_B;
@@ -1018,13 +1092,20 @@ __device__ __forceinline__ FetchSpan fetch_decode_span(const DcFetchSrc& S, int6
             }
             const int64_t o = boff[b] + wave_incl_add(contrib) - contrib;
             const int64_t p = S.bdsum[b] + wave_incl_add(d);   // running p, this token included
-            if (!tok && contrib == 1 && c != '(' && o >= d0 && o < d1) sdec[o - d0] = c;
+            if (!tok && contrib == 1 && c != '(' && o >= d0 && o < d1) {
+                if (ORIGIN) org[opad((int)(o - d0))] = -1;
+                else sdec[o - d0] = c;
+            }
             unsigned long long tm = __ballot(tok && o < d1 && o + contrib > d0);
             while (tm) {
                 const int j = __ffsll((long long)tm) - 1;   // (wave-uniform: the token's fields by readlane)
                 tm &= tm - 1;
                 const int64_t pj = readlane64(p, j), oj = readlane64(o, j), lj = readlane64(contrib, j);
                 const int64_t a = oj > d0 ? oj : d0, e = oj + lj < d1 ? oj + lj : d1;
+                if (ORIGIN) {   // (the open's range check: pj + lj <= |R'| <= |R| < 2^31)
+                    origin_piece(S.rm, pj + (a - oj), (int)(e - a), org, (int)(a - d0), *mc);
+                    continue;
+                }
                 const uint8_t* __restrict__ src = S.R + pj + (a - oj);   // not walked there from the token's start
                 uint8_t* dst = sdec + (a - d0);
                 const int cnt = (int)(e - a), k = lane * OPT;   // cnt <= FT_W: one 16-byte load per lane
@@ -1420,9 +1501,214 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_cohort(const FetchCohortAr
     fetch_enc_stream<ENC, DT>(fw, base, w0, fend, A.elemwise, A.out, lane);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Origin fetch (SCCG_ENC_ORIGIN): k_fetch_enc's geometry -- a wave owns FT_W bases -- with one int32
+// per base saying where the base comes from: the position in the reference sequence R a token copied
+// it from, -1 for a literal of the record line, -2 for a base of one of the target's N runs.
+// fetch_decode_span<true> leaves R positions (or -1) in the wave's int32 tile, mapped from R' once per
+// token piece (origin_piece); R' itself is never loaded.  A lane walks its bases through the target's
+// N runs as fetch_enc_walk does and places each value.  The finished tile streams out as
+// k_fetch_enc's does: 16-byte pieces of 4 bases, piece q to lane q % 64, element stores for the
+// pieces the tile's ends cut.  One kernel for the reader (the source in the arguments) and the
+// cohort (COHORT: the source of each span from the table, as in k_fetch_cohort).
+// LDS per block: WPB x (2 x FO_TILE x 4 + 2 x TK_B) = 35,328 bytes -> 4 blocks of a CU's 160 KiB,
+// 16 waves per CU, 4 per SIMD.
+// ---------------------------------------------------------------------------------------------
+struct FetchOriginArgs {
+    DcCohortEntry E;            // the reader's source (!COHORT)
+    const DcCohortEntry* tab;   // one entry per sample (COHORT)
+    const int64_t* pre;         // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
+    const int64_t* beg;         // nreg: region begins, bit 63 set = reverse strand
+    const int32_t* samp;        // nreg: region samples (COHORT)
+    int64_t nreg, F, o_first;   // o_first: the flat base of block 0's first base (<= 0)
+    uint32_t all_rev;
+    int32_t* out;
+};
+
+// A lane's bases of one span: positions j, j + 1, ... through the target's N runs from rn, each
+// origin at its output place mine[k0, k1) (opad'ed from the lane's first entry m0) -- descending for
+// a reversed span; the value itself is the same on either strand.
+__device__ __forceinline__ void fetch_origin_walk(const DcFetchSrc& S, int64_t nn, int64_t ntot, const int32_t* org, int32_t* fw,
+                                                  int m0, int64_t j, int64_t rn, int64_t d0, bool rev, int k0, int k1) {
+    const int32_t* __restrict__ ns = S.nr.start;
+    const int32_t* __restrict__ nl = S.nr.len;
+    const int64_t* __restrict__ ncum = S.nr.cum;
+    int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot;
+    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+    for (int t = 0; t < k1 - k0; t++) {
+        while (j >= n_e) {
+            rn++;
+            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+            else { n_s = n_e = INT64_MAX; n_b = ntot; }
+        }
+        const int32_t v = j < n_s ? org[opad((int)(j - n_b - d0))] : -2;
+        j++;
+        fw[opad(m0 + (rev ? k1 - 1 - t : k0 + t))] = v;
+    }
+}
+
+template <bool COHORT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_origin(const FetchOriginArgs A) {
+    __shared__ int32_t tile[WPB][FO_TILE];
+    __shared__ int32_t fin[WPB][FO_TILE];
+    __shared__ uint8_t stg[WPB][2 * TK_B];
+    const int lane = lane_id();
+    int32_t* org = tile[wave_in_block()];
+    int32_t* fw = fin[wave_in_block()];
+    uint8_t* st = stg[wave_in_block()];
+    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
+    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
+    const int64_t w0 = base < 0 ? 0 : base;
+    int64_t f = w0;
+    if (f >= fend) return;
+    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
+    const int64_t* __restrict__ pre = A.pre;
+    DcCohortEntry E = A.E;   // the current span's sample
+    int cur = -1;
+    MapCur mc{0, INT64_MAX, INT64_MAX, 0};   // (no bracket yet: the first piece searches)
+    const int32_t* mc_of = nullptr;          // the map mc brackets (the readers of one shared reference have one)
+    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+    while (f < fend) {
+        if (pre[i + 1] <= f) {
+            i++;
+            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
+        }
+        if (COHORT) {
+            const int sm = __builtin_amdgcn_readfirstlane(A.samp[i]);
+            if (sm != cur) {   // (wave-uniform: a scalar branch around scalar loads)
+                cur = sm;
+                E = cohort_entry(A.tab, sm);
+            }
+        }
+        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
+        const int64_t braw = A.beg[i];
+        const bool rev = A.all_rev || braw < 0;
+        const int64_t bg = braw & INT64_MAX;
+        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
+        if (E.S.rm.start != mc_of) {
+            mc = MapCur{0, INT64_MAX, INT64_MAX, 0};
+            mc_of = E.S.rm.start;
+        }
+        const FetchSpan sp = fetch_decode_span<true>(E.S, j0, j1, reinterpret_cast<uint8_t*>(org), st, &mc);
+        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
+        if (ga < gb) {
+            const int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f);
+            fetch_origin_walk(E.S, E.nn, E.ntot, org, fw, lane * OPT, j, sp.rn0, sp.d0, rev, (int)(ga - g0), (int)(gb - g0));
+        }
+        wave_sync();   // (the tile is read before the next span fills it)
+        f = fe;
+    }
+    wave_sync();   // fin[w0 - base, fend - base) is complete
+    for (int it = 0; it < 4 * (FT_W / 256); it++) {
+        const int q = it * 64 + lane;
+        const int64_t p0 = base + (int64_t)q * 4;   // the piece's first base
+        if (p0 >= fend || p0 + 4 <= w0) continue;
+        int32_t w[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) w[t] = fw[opad(q * 4 + t)];
+        int32_t* dst = A.out + p0;
+        if (p0 >= w0 && p0 + 4 <= fend) {
+            *reinterpret_cast<int4*>(dst) = make_int4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                if (p0 + t >= w0 && p0 + t < fend) dst[t] = w[t];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The R' -> R map of a shared reference: the maximal runs of the byte 'N' (uppercase only: a
+// lowercase 'n' survives into R' as "N", decompression.cpp:108 before :110) in the stripped,
+// original-case reference R.  A block takes RM_TILE bytes, a thread 16 of them in one load; a run
+// starts where an 'N' follows another byte and ends where another byte follows it, so starts and
+// ends are counted per tile, ranked by two prefix sums over the tiles and written in a second pass
+// (start k pairs with end k), whatever the runs' lengths are.
+// ---------------------------------------------------------------------------------------------
+constexpr int RM_PER = 16, RM_TILE = SCCG_BLOCK * RM_PER;
+
+// bit k of st / en: byte i0 + k of R starts / ends a run
+__device__ __forceinline__ void refn_events(const uint8_t* __restrict__ R, int64_t n, int64_t i0, uint32_t& st, uint32_t& en) {
+    st = en = 0;
+    if (i0 >= n) return;
+    const uint4 x = load16u(R + i0);   // (past n: R carries the slack)
+    const uint32_t w4[4] = {x.x, x.y, x.z, x.w};
+    uint32_t isn = 0;
+#pragma unroll
+    for (int k = 0; k < RM_PER; k++)
+        if (i0 + k < n && (uint8_t)(w4[k >> 2] >> (8 * (k & 3))) == 'N') isn |= 1u << k;
+    const uint32_t prev = i0 > 0 && R[i0 - 1] == 'N', next = i0 + RM_PER < n && R[i0 + RM_PER] == 'N';
+    st = isn & ~((isn << 1) | prev);
+    en = isn & ~((isn >> 1) | (next << (RM_PER - 1)));
+}
+
+__global__ __launch_bounds__(SCCG_BLOCK) void k_refn_count(const uint8_t* __restrict__ R, int64_t n, int64_t* __restrict__ cs,
+                                                           int64_t* __restrict__ ce) {
+    __shared__ int64_t tmp[5];
+    uint32_t st, en;
+    refn_events(R, n, ((int64_t)blockIdx.x * SCCG_BLOCK + threadIdx.x) * RM_PER, st, en);
+    int64_t ts = 0, te = 0;
+    block_excl_add<int64_t>(__popc(st), tmp, &ts);
+    block_excl_add<int64_t>(__popc(en), tmp, &te);
+    if (threadIdx.x == 0) {
+        cs[blockIdx.x] = ts;
+        ce[blockIdx.x] = te;
+    }
+}
+
+// start[k] = the k-th run's first byte, end[k] = its last (inclusive); os / oe: the tiles' ranks
+__global__ __launch_bounds__(SCCG_BLOCK) void k_refn_write(const uint8_t* __restrict__ R, int64_t n, const int64_t* __restrict__ os,
+                                                           const int64_t* __restrict__ oe, int64_t nruns,
+                                                           int32_t* __restrict__ start, int32_t* __restrict__ end) {
+    __shared__ int64_t tmp[5];
+    uint32_t st, en;
+    const int64_t i0 = ((int64_t)blockIdx.x * SCCG_BLOCK + threadIdx.x) * RM_PER;
+    refn_events(R, n, i0, st, en);
+    int64_t rs = os[blockIdx.x] + block_excl_add<int64_t>(__popc(st), tmp, nullptr);
+    int64_t re = oe[blockIdx.x] + block_excl_add<int64_t>(__popc(en), tmp, nullptr);
+    for (; st; st &= st - 1, rs++)
+        if (rs < nruns) start[rs] = (int32_t)(i0 + __ffs((int)st) - 1);
+    for (; en; en &= en - 1, re++)
+        if (re < nruns) end[re] = (int32_t)(i0 + __ffs((int)en) - 1);
+}
+
+// len[k] <- end[k] - start[k] + 1 (len holds the ends on entry), cum[k] <- the same, to be summed
+__global__ void k_refn_len(const int32_t* __restrict__ start, int32_t* __restrict__ len, int64_t* __restrict__ cum, int64_t nruns) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nruns; k += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t l = len[k] - start[k] + 1;
+        len[k] = l;
+        cum[k] = l;
+    }
+}
+
 }  // namespace
 
 // =============================================================================================
+int64_t dc_refmap_tiles(int64_t n) { return n > 0 ? (n + RM_TILE - 1) / RM_TILE : 0; }
+
+int dc_refmap_count(const uint8_t* d_R, int64_t n, int64_t* d_cs, int64_t* d_ce, int64_t* d_os, int64_t* d_oe, int64_t* d_nruns,
+                    int64_t* d_partial, hipStream_t s) {
+    const int64_t nt = dc_refmap_tiles(n);
+    if (!nt) {
+        SCCG_HIP(hipMemsetAsync(d_nruns, 0, 2 * sizeof(int64_t), s));
+        return 0;
+    }
+    hipLaunchKernelGGL(k_refn_count, dim3((unsigned)nt), dim3(SCCG_BLOCK), 0, s, d_R, n, d_cs, d_ce);
+    SCCG_HIP(hipGetLastError());
+    return dev_excl_sum2(d_cs, d_os, d_nruns, d_ce, d_oe, d_nruns + 1, nt, d_partial, s);
+}
+
+int dc_refmap_write(const uint8_t* d_R, int64_t n, const int64_t* d_os, const int64_t* d_oe, DcRuns* m, int64_t* d_total,
+                    int64_t* d_partial, hipStream_t s) {
+    if (m->n <= 0) return 0;
+    hipLaunchKernelGGL(k_refn_write, dim3((unsigned)dc_refmap_tiles(n)), dim3(SCCG_BLOCK), 0, s, d_R, n, d_os, d_oe, m->n, m->start,
+                       m->len);
+    const unsigned g = grid_for(m->n, 256) > 4096 ? 4096 : grid_for(m->n, 256);
+    hipLaunchKernelGGL(k_refn_len, dim3(g), dim3(256), 0, s, (const int32_t*)m->start, m->len, m->cum, m->n);
+    SCCG_HIP(hipGetLastError());
+    return dev_excl_sum(m->cum, m->cum, m->n, d_total, d_partial, s);
+}
+
 int dc_find_lines(const uint8_t* d_rec, int64_t n, int64_t* d_nl /*8: 4 results + 4 tickets*/, hipStream_t s) {
     for (int i = 0; i < 4; i++) {
         int rc = launch_first_match(d_rec, n, i ? (const int64_t*)(d_nl + i - 1) : nullptr, 1, '\n', d_nl + i, d_nl + 4 + i, s);
@@ -1661,6 +1947,28 @@ int dc_fetch_cohort(const DcCohortEntry* d_tab, const int64_t* d_pre, const int6
     else if (enc == FE_ONEHOT && dt == FD_F32) SCCG_FETCH_COHORT(FE_ONEHOT, FD_F32);
     else return SCCG_E_INVALID;
 #undef SCCG_FETCH_COHORT
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
+int dc_fetch_origin(const DcFetchSrc* src, const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg,
+                    const int32_t* d_samp, int64_t nreg, int64_t F, bool all_rev, int32_t* d_out, hipStream_t s) {
+    if (F <= 0) return 0;
+    if ((uintptr_t)d_out & 3) return SCCG_E_INVALID;
+    FetchOriginArgs A{};
+    if (src) A.E = DcCohortEntry{*src, src->nr.n, src->lr.n, src->nr.total};
+    A.tab = d_tab;
+    A.pre = d_pre;
+    A.beg = d_beg;
+    A.samp = d_samp;
+    A.nreg = nreg;
+    A.F = F;
+    A.o_first = -(int64_t)(((uintptr_t)d_out & 15) / 4);   // whole 16-byte pieces of 4 bases
+    A.all_rev = all_rev ? 1u : 0u;
+    A.out = d_out;
+    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
+    if (src) PROF_LAUNCH(PROF_FETCH, s, (k_fetch_origin<false>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
+    else PROF_LAUNCH(PROF_FETCH, s, (k_fetch_origin<true>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
     SCCG_HIP(hipGetLastError());
     return 0;
 }

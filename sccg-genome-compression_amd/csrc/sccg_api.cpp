@@ -225,6 +225,10 @@ struct sccg_reference {
     sccg_ctx* ctx = nullptr;
     void* mem[2] = {nullptr, nullptr};
     size_t bytes[2] = {0, 0};   // of each allocation; 0: the form is not held
+    bool coords = false;        // opened with SCCG_REF_COORDS: `map` is the erased form's R' -> R map
+    void* map_mem = nullptr;    // the map's arrays (start, len, cum), when R holds an 'N' run
+    size_t map_bytes = 0;
+    DcRuns map{};               // the runs of 'N' in R
     int64_t holds = 1;          // the caller's (until sccg_reference_close) + one per reader
     const int64_t* d_len(int form) const {
         return reinterpret_cast<const int64_t*>(reinterpret_cast<const uint8_t*>(mem[form]) + bytes[form] - 256);
@@ -240,6 +244,7 @@ struct sccg_reader {
     void* mem = nullptr;        // R' (a private open), the record line, its block index, both run lists (src points into it)
     DcFetchSrc src{};
     int64_t length = 0;         // bases in the sequence (reconstruct_impl's nres)
+    bool has_coords = false;    // src.rm turns R' positions into the reference's (the origin fetch)
     std::string header;         // the header line, '>' included, no '\n'; empty: none
     void* d_reg = nullptr;      // a fetch's region list: device copy and its pinned host image
     int64_t* h_reg = nullptr;
@@ -253,6 +258,7 @@ struct sccg_reader {
 struct sccg_cohort {
     sccg_ctx* ctx = nullptr;
     std::vector<int64_t> length;   // per sample
+    std::vector<uint8_t> coords;   // per sample: its reader has reference coordinates
     void* d_tab = nullptr;         // DcCohortEntry per sample
     void* d_reg = nullptr;         // a fetch's region list: device copy and its pinned host image
     int64_t* h_reg = nullptr;
@@ -1501,6 +1507,9 @@ int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
         rd->ref = ref;
         ref->holds++;
     }
+    // reference coordinates: the kept form is R itself; the erased form needs the reference's map
+    rd->has_coords = form == REF_KEPT || (ref && ref->coords);
+    if (form == REF_ERASED && ref && ref->coords) S.rm = ref->map;
     S.nr = DcRuns{reinterpret_cast<int32_t*>(m + o_ns), reinterpret_cast<int32_t*>(m + o_nl),
                   reinterpret_cast<int64_t*>(m + o_nc), nr.n, nr.total};
     S.lr = DcRuns{reinterpret_cast<int32_t*>(m + o_ls), reinterpret_cast<int32_t*>(m + o_ll), nullptr, lr.n, lr.total};
@@ -1553,8 +1562,23 @@ int fetch_check(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t* 
 size_t fetch_format_bpb(const sccg_fetch_format* f) {
     if (!f || f->reserved || (f->flags & ~(SCCG_FETCH_UPPER | SCCG_FETCH_REVCOMP))) return 0;
     if (f->encoding == SCCG_ENC_ASCII || f->encoding == SCCG_ENC_INDEX) return f->dtype == SCCG_DT_U8 ? 1 : 0;
+    if (f->encoding == SCCG_ENC_ORIGIN) return f->dtype == SCCG_DT_I32 ? 4 : 0;
     if (f->encoding != SCCG_ENC_ONEHOT) return 0;
     return f->dtype == SCCG_DT_U8 ? 4 : f->dtype == SCCG_DT_F16 || f->dtype == SCCG_DT_BF16 ? 8 : f->dtype == SCCG_DT_F32 ? 16 : 0;
+}
+
+// the element d_out must be aligned to
+size_t fetch_format_elem(const sccg_fetch_format* f, size_t bpb) {
+    return f->encoding == SCCG_ENC_ONEHOT ? bpb / 4 : f->encoding == SCCG_ENC_ORIGIN ? 4 : 1;
+}
+
+// an ORIGIN fetch needs a reader with reference coordinates (checked after the format, for ORIGIN only)
+int fetch_coords_check(sccg_reader* rd, const sccg_fetch_format* fmt) {
+    if (fmt->encoding != SCCG_ENC_ORIGIN || rd->has_coords) return SCCG_OK;
+    return rd->ctx->fail(SCCG_E_UNSUPPORTED,
+                         rd->ref ? "the reader has no reference coordinates: its reference was opened without SCCG_REF_COORDS"
+                                 : "the reader has no reference coordinates: a private reader of a record with an N-run line "
+                                   "(open it through a sccg_reference with SCCG_REF_COORDS)");
 }
 
 // regions validated, F > 0, d_out holds the output: the region list in one copy, one launch, one
@@ -1587,7 +1611,10 @@ int fetch_run(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t F, 
     h[n] = at;
     int64_t* d = reinterpret_cast<int64_t*>(rd->d_reg);
     HIPTRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    if (fmt)
+    if (fmt && fmt->encoding == SCCG_ENC_ORIGIN)
+        TRY(dc_fetch_origin(&rd->src, nullptr, d, d + n + 1, nullptr, (int64_t)n, F, (flags & SCCG_FETCH_REVCOMP) != 0,
+                            reinterpret_cast<int32_t*>(d_out), s));
+    else if (fmt)
         TRY(dc_fetch_encoded(rd->src, d, d + n + 1, (int64_t)n, F, (int)fmt->encoding, (int)fmt->dtype,
                              (flags & SCCG_FETCH_UPPER) != 0, (flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
     else
@@ -1605,7 +1632,41 @@ void reference_drop(sccg_reference* ref) {
     (void)hipSetDevice(ref->ctx->device);
     for (int f = 0; f < 2; f++)
         if (ref->mem[f]) (void)hipFree(ref->mem[f]);
+    if (ref->map_mem) (void)hipFree(ref->map_mem);
     delete ref;
+}
+
+// The R' -> R map (SCCG_REF_COORDS): the runs of 'N' in the stripped, original-case reference
+// R[0, nR), counted, sized (one read of the count), written into an allocation of the reference's
+// own.  No run: no allocation, and R' is R.
+int reference_map(sccg_ctx* ctx, const uint8_t* R, int64_t nR, int64_t* sc, sccg_reference* ref) {
+    hipStream_t s = ctx->stream;
+    if (nR >= (int64_t)INT32_MAX)
+        return ctx->fail(SCCG_E_UNSUPPORTED, "SCCG_REF_COORDS takes a reference of fewer than 2^31 - 1 bases (this one has %lld)",
+                         (long long)nR);
+    const int64_t nt = dc_refmap_tiles(nR);
+    GET(int64_t, tl, B_TMP64, 4 * nt + 4);
+    GET(int64_t, part, B_PARTIAL, 2 * scan_partials_needed(nt + 1) + 16);
+    TRY(dc_refmap_count(R, nR, tl, tl + nt, tl + 2 * nt, tl + 3 * nt, sc + 24, part, s));
+    int64_t nruns[2] = {0, 0};
+    {
+        const RbItem it{sc + 24, nruns, (int)sizeof nruns};
+        TRY(dev_readback(&it, 1, s));
+    }
+    if (nruns[0] != nruns[1]) return ctx->fail(SCCG_E_INTERNAL, "reference map: %lld run starts, %lld run ends", (long long)nruns[0], (long long)nruns[1]);
+    if (!nruns[0]) return SCCG_OK;
+    const size_t n = (size_t)nruns[0], a4 = (n * 4 + 255) & ~(size_t)255, bytes = 2 * a4 + ((n * 8 + 255) & ~(size_t)255);
+    const hipError_t e = hipMalloc(&ref->map_mem, bytes);
+    if (e != hipSuccess) { ref->map_mem = nullptr; return reader_alloc_fail(ctx, e, bytes); }
+    ref->map_bytes = bytes;
+    uint8_t* m = reinterpret_cast<uint8_t*>(ref->map_mem);
+    ref->map = DcRuns{reinterpret_cast<int32_t*>(m), reinterpret_cast<int32_t*>(m + a4), reinterpret_cast<int64_t*>(m + 2 * a4),
+                      (int64_t)n, 0};
+    GET(int64_t, part2, B_PARTIAL, scan_partials_needed((int64_t)n + 1) + 16);
+    TRY(dc_refmap_write(R, nR, tl + 2 * nt, tl + 3 * nt, &ref->map, sc + 26, part2, s));
+    const RbItem it{sc + 26, &ref->map.total, (int)sizeof(int64_t)};
+    TRY(dev_readback(&it, 1, s));
+    return SCCG_OK;
 }
 
 // each form asked for by the strip call reader_open_impl makes for it, into an allocation of its own
@@ -1613,13 +1674,22 @@ int reference_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, uint32_t 
     hipStream_t s = ctx->stream;
     GET(int64_t, sc, B_SCAL, 64);
     GET(uint8_t, Rp, B_RP, rn + 64);
+    ref->coords = (forms & SCCG_REF_COORDS) != 0;
     for (int f = 0; f < 2; f++) {
         if (!(forms & (f == REF_KEPT ? SCCG_REF_KEPT : SCCG_REF_ERASED))) continue;
-        TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, nullptr, sc + 8, nullptr, nullptr,
+        // the map is made from R in its original case, which the erased form's strip writes beside R'
+        uint8_t* R = nullptr;
+        if (ref->coords && f == REF_ERASED) {
+            GET(uint8_t, R1, B_R, rn + 64);
+            R = R1;
+        }
+        TRY(strip(ctx, INGEST_REF, rfa, rn, nullptr, R, sc + 8, nullptr, nullptr,
                   f == REF_KEPT ? FILTER_UPPER : FILTER_DROP_UPPERN_ONLY, Rp, 1, s));
-        int64_t nRp = 0;
-        const RbItem it{sc + 9, &nRp, (int)sizeof nRp};
+        int64_t lens[2] = {0, 0};   // |R|, |R'|
+        const RbItem it{sc + 8, lens, (int)sizeof lens};
         TRY(dev_readback(&it, 1, s));
+        const int64_t nRp = lens[1];
+        if (R) TRY(reference_map(ctx, R, lens[0], sc, ref));
         // R', DPAD of readable slack, and |R'| in the last 256-byte part
         const size_t bytes = (((size_t)nRp + DPAD + 255) & ~(size_t)255) + 256;
         const hipError_t e = hipMalloc(&ref->mem[f], bytes);
@@ -1676,6 +1746,9 @@ int cohort_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, c
         if (r.begin < 0 || r.end < r.begin || r.end > len)
             return ctx->fail(SCCG_E_INVALID, "region %zu [%lld, %lld) is outside sample %d's sequence [0, %lld)", i,
                              (long long)r.begin, (long long)r.end, (int)r.sample, (long long)len);
+        if (fmt->encoding == SCCG_ENC_ORIGIN && !co->coords[(size_t)r.sample])
+            return ctx->fail(SCCG_E_UNSUPPORTED, "region %zu reads sample %d, whose reader has no reference coordinates "
+                             "(open it through a sccg_reference with SCCG_REF_COORDS)", i, (int)r.sample);
         tot += r.end - r.begin;
     }
     *F = tot;
@@ -1712,9 +1785,14 @@ int cohort_run(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, int
     h[n] = at;
     int64_t* d = reinterpret_cast<int64_t*>(co->d_reg);
     HIPTRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    TRY(dc_fetch_cohort(reinterpret_cast<const DcCohortEntry*>(co->d_tab), d, d + n + 1, reinterpret_cast<const int32_t*>(d + words),
-                        (int64_t)n, F, (int)fmt->encoding, (int)fmt->dtype, (fmt->flags & SCCG_FETCH_UPPER) != 0,
-                        (fmt->flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
+    if (fmt->encoding == SCCG_ENC_ORIGIN)
+        TRY(dc_fetch_origin(nullptr, reinterpret_cast<const DcCohortEntry*>(co->d_tab), d, d + n + 1,
+                            reinterpret_cast<const int32_t*>(d + words), (int64_t)n, F, (fmt->flags & SCCG_FETCH_REVCOMP) != 0,
+                            reinterpret_cast<int32_t*>(d_out), s));
+    else
+        TRY(dc_fetch_cohort(reinterpret_cast<const DcCohortEntry*>(co->d_tab), d, d + n + 1,
+                            reinterpret_cast<const int32_t*>(d + words), (int64_t)n, F, (int)fmt->encoding, (int)fmt->dtype,
+                            (fmt->flags & SCCG_FETCH_UPPER) != 0, (fmt->flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
     HIPTRY(hipStreamSynchronize(s));
     return SCCG_OK;
 }
@@ -1865,6 +1943,8 @@ void sccg_reader_close(sccg_reader* reader) { reader_free(reader); }
 
 int64_t sccg_reader_length(const sccg_reader* reader) { return reader ? reader->length : -1; }
 
+int sccg_reader_has_coords(const sccg_reader* reader) { return reader && reader->has_coords ? 1 : 0; }
+
 const char* sccg_reader_header(const sccg_reader* reader, size_t* len) {
     if (len) *len = reader ? reader->header.size() : 0;
     return reader ? reader->header.c_str() : "";
@@ -1924,10 +2004,11 @@ int sccg_reader_fetch_encoded_device(sccg_reader* reader, const sccg_region* reg
     const size_t bpb = fetch_format_bpb(fmt);
     if (!bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
                                fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
-    const size_t es = fmt->encoding == SCCG_ENC_ONEHOT ? bpb / 4 : 1;
+    const size_t es = fetch_format_elem(fmt, bpb);
     if ((uintptr_t)d_out % es) return ctx->fail(SCCG_E_INVALID, "d_out is not aligned to the %zu-byte element", es);
     int64_t F = 0;
-    const int rc = fetch_check(reader, regions, n, &F);
+    int rc = fetch_coords_check(reader, fmt);
+    if (!rc) rc = fetch_check(reader, regions, n, &F);
     if (rc) return rc;
     *out_len = (size_t)F * bpb;
     if (!d_out) return SCCG_OK;   // size query
@@ -1945,7 +2026,8 @@ int sccg_reader_fetch_encoded(sccg_reader* reader, const sccg_region* regions, s
     if (!bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
                                fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
     int64_t F = 0;
-    int rc = fetch_check(reader, regions, n, &F);
+    int rc = fetch_coords_check(reader, fmt);
+    if (!rc) rc = fetch_check(reader, regions, n, &F);
     if (rc) return rc;   // (nothing written: *out is the caller's as it was)
     const size_t bytes = (size_t)F * bpb;
     char* h = (char*)malloc(bytes + 1);
@@ -1976,8 +2058,9 @@ int sccg_reference_open_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_l
                                void* stream) {
     if (out) *out = nullptr;
     if (!ctx || !out || (!d_ref_fa && ref_len)) return SCCG_E_INVALID;
-    if (forms & ~(SCCG_REF_ERASED | SCCG_REF_KEPT)) return ctx->fail(SCCG_E_INVALID, "unknown reference form bits (forms %u)", forms);
-    if (!forms) forms = SCCG_REF_ERASED | SCCG_REF_KEPT;
+    if (forms & ~(SCCG_REF_ERASED | SCCG_REF_KEPT | SCCG_REF_COORDS))
+        return ctx->fail(SCCG_E_INVALID, "unknown reference form bits (forms %u)", forms);
+    if (!(forms & (SCCG_REF_ERASED | SCCG_REF_KEPT))) forms |= SCCG_REF_ERASED | SCCG_REF_KEPT;   // (no form named: both)
     HIPTRY(hipSetDevice(ctx->device));
     hipStream_t saved = ctx->stream;
     if (stream) ctx->stream = (hipStream_t)stream;
@@ -2000,7 +2083,7 @@ void sccg_reference_close(sccg_reference* ref) {
     if (ref) reference_drop(ref);
 }
 
-size_t sccg_reference_device_bytes(const sccg_reference* ref) { return ref ? ref->bytes[0] + ref->bytes[1] : 0; }
+size_t sccg_reference_device_bytes(const sccg_reference* ref) { return ref ? ref->bytes[0] + ref->bytes[1] + ref->map_bytes : 0; }
 
 int sccg_reader_open_shared_device(sccg_reference* ref, const void* d_rec, size_t rec_len, sccg_reader** out, void* stream) {
     if (out) *out = nullptr;
@@ -2041,10 +2124,12 @@ int sccg_cohort_create(sccg_reader* const* readers, size_t n_samples, sccg_cohor
     sccg_cohort* co = new sccg_cohort();
     co->ctx = ctx;
     co->length.resize(n_samples);
+    co->coords.resize(n_samples);
     for (size_t i = 0; i < n_samples; i++) {
         const DcFetchSrc& S = readers[i]->src;
         tab[i] = DcCohortEntry{S, S.nr.n, S.lr.n, S.nr.total};
         co->length[i] = readers[i]->length;
+        co->coords[i] = readers[i]->has_coords ? 1 : 0;
     }
     const size_t bytes = n_samples * sizeof(DcCohortEntry);
     hipError_t e = hipMalloc(&co->d_tab, bytes);
@@ -2074,7 +2159,7 @@ int sccg_cohort_fetch_device(sccg_cohort* cohort, const sccg_cohort_region* regi
     int64_t F = 0;
     const size_t bpb0 = fetch_format_bpb(fmt);
     if (bpb0) {
-        const size_t es = fmt->encoding == SCCG_ENC_ONEHOT ? bpb0 / 4 : 1;
+        const size_t es = fetch_format_elem(fmt, bpb0);
         if ((uintptr_t)d_out % es) return ctx->fail(SCCG_E_INVALID, "d_out is not aligned to the %zu-byte element", es);
     }
     const int rc = cohort_check(cohort, regions, n, fmt, &bpb, &F);

@@ -22,8 +22,10 @@ OPT_EXACT_SWITCH = 1   # sccg_ctx_set_option (include/sccg.h)
 FETCH_UPPER = 1        # sccg_reader_fetch flags
 FETCH_REVCOMP = 2      # sccg_reader_fetch_encoded: every region on the reverse strand
 REF_FORMS = {"erased": 1, "kept": 2}                       # SCCG_REF_*: which R' a record's N line asks for
-ENCODINGS = {"ascii": 0, "index": 1, "onehot": 2}          # SCCG_ENC_*
-DTYPES = {"u8": 0, "f16": 1, "bf16": 2, "f32": 3}          # SCCG_DT_*
+REF_COORDS = 4                                             # SCCG_REF_COORDS: keep the R' -> R map (origin fetch)
+ENCODINGS = {"ascii": 0, "index": 1, "onehot": 2, "origin": 3}     # SCCG_ENC_*
+DTYPES = {"u8": 0, "f16": 1, "bf16": 2, "f32": 3, "i32": 4}        # SCCG_DT_* ("i32": with "origin" only)
+ORIGIN_LITERAL, ORIGIN_N = -1, -2                          # "origin" values that are no reference position
 ERRORS = {1: "SCCG_E_INVALID", 2: "SCCG_E_HIP", 3: "SCCG_E_NOMEM", 4: "SCCG_E_DELTA_STOI",
           5: "SCCG_E_FORMAT", 6: "SCCG_E_RANGE", 7: "SCCG_E_PARSE", 8: "SCCG_E_UNSUPPORTED",
           9: "SCCG_E_INTERNAL", 10: "SCCG_E_OPEN_REF", 11: "SCCG_E_OPEN_TGT", 12: "SCCG_E_WRITE"}
@@ -152,6 +154,9 @@ def load_library():
         lib.sccg_reader_close.restype = None
         lib.sccg_reader_length.argtypes = [vp]
         lib.sccg_reader_length.restype = i64
+        if hasattr(lib, "sccg_reader_has_coords"):
+            lib.sccg_reader_has_coords.argtypes = [vp]
+            lib.sccg_reader_has_coords.restype = ctypes.c_int
         lib.sccg_reader_header.argtypes = [vp, ctypes.POINTER(sz)]
         lib.sccg_reader_header.restype = vp
         lib.sccg_reader_fetch.argtypes = [vp, ctypes.POINTER(Region), sz, ctypes.c_uint32, ctypes.POINTER(Buf)]
@@ -346,20 +351,24 @@ class Context:
             mask |= REF_FORMS[f]
         return mask
 
-    def open_reference(self, ref_fa: bytes, forms=("erased", "kept")) -> "Reference":
+    def open_reference(self, ref_fa: bytes, forms=("erased", "kept"), coords: bool = False) -> "Reference":
         """A shared reference (sccg_reference_open): R' held once for every reader opened through it.
-        forms: "erased" (records with an N-run line), "kept" (records whose N line is ","), or both."""
+        forms: "erased" (records with an N-run line), "kept" (records whose N line is ","), or both.
+        coords: also keep the R' -> R map (SCCG_REF_COORDS), so that readers of erased-form records
+        can say where on the reference a base comes from (the "origin" encoding)."""
         ptr = ctypes.c_void_p()
-        rc = self.lib.sccg_reference_open(self.ptr, ref_fa, len(ref_fa), self._forms(forms), ctypes.byref(ptr))
+        rc = self.lib.sccg_reference_open(self.ptr, ref_fa, len(ref_fa), self._forms(forms) | (REF_COORDS if coords else 0),
+                                          ctypes.byref(ptr))
         if rc:
             self._err(rc)
         return Reference(self, ptr)
 
-    def open_reference_device(self, d_ref: int, ref_len: int, forms=("erased", "kept"), stream: int = 0) -> "Reference":
+    def open_reference_device(self, d_ref: int, ref_len: int, forms=("erased", "kept"), stream: int = 0,
+                              coords: bool = False) -> "Reference":
         """open_reference on a device-resident FASTA (sccg_reference_open_device)."""
         ptr = ctypes.c_void_p()
-        rc = self.lib.sccg_reference_open_device(self.ptr, d_ref, ref_len, self._forms(forms), ctypes.byref(ptr),
-                                                 stream or None)
+        rc = self.lib.sccg_reference_open_device(self.ptr, d_ref, ref_len, self._forms(forms) | (REF_COORDS if coords else 0),
+                                                 ctypes.byref(ptr), stream or None)
         if rc:
             self._err(rc)
         return Reference(self, ptr)
@@ -506,6 +515,12 @@ class Reader:
         return self.lib.sccg_reader_length(self.ptr)
 
     @property
+    def has_coords(self) -> bool:
+        """Whether the "origin" encoding works on this reader (sccg_reader_has_coords): its record's N
+        line is ",", or it was opened through a Reference with coords=True."""
+        return bool(self.lib.sccg_reader_has_coords(self.ptr))
+
+    @property
     def device_bytes(self) -> int:
         """The reader's own persistent device allocation (sccg_reader_device_bytes): without R' when
         it was opened through a Reference."""
@@ -572,7 +587,10 @@ class Reader:
         """The regions' bases concatenated and encoded (sccg_reader_fetch_encoded): "ascii" and
         "index" (A 0, C 1, G 2, T 3, other 4) one byte per base, "onehot" four `dtype` elements per
         base.  strand: one truthy / falsy value per region, truthy = reverse complement; revcomp:
-        all of them."""
+        all of them.  "origin" (dtype "i32"): one little-endian int32 per base -- the 0-based
+        position in the reference sequence a token copied it from, ORIGIN_LITERAL (-1) for a literal of
+        the record, ORIGIN_N (-2) inside one of the target's N runs; a reversed region's values come
+        in reverse order, unchanged.  It needs has_coords."""
         regions, arr = self._regions(regions)
         fmt = self._format(encoding, dtype, revcomp, upper)
         buf = Buf()
@@ -600,13 +618,17 @@ class Reader:
         return n.value
 
     def fetch_tensor(self, regions, encoding: str = "onehot", dtype=None, strand=None, revcomp: bool = False, stream=None):
-        """A torch tensor on the context's device: [n, L] ("index", "ascii": uint8) or [n, L, 4]
+        """A torch tensor on the context's device: [n, L] ("index", "ascii": uint8; "origin": int32) or [n, L, 4]
         ("onehot": dtype, default torch.float16) when every region has the same length L, else flat
         [F] / [F, 4].  stream: a torch stream (default: the current one)."""
         import torch
         regions = [(int(b), int(e)) for b, e in regions]
-        names = {torch.uint8: "u8", torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32"}
-        if encoding != "onehot":
+        names = {torch.uint8: "u8", torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32", torch.int32: "i32"}
+        if encoding == "origin":
+            dtype = torch.int32 if dtype is None else dtype
+            if dtype != torch.int32:
+                raise ValueError("'origin' is int32")
+        elif encoding != "onehot":
             dtype = torch.uint8 if dtype is None else dtype
             if dtype != torch.uint8:
                 raise ValueError(f"{encoding!r} is uint8")
@@ -698,8 +720,12 @@ class Cohort:
         length L, else flat [F] / [F, 4]."""
         import torch
         items = [tuple(it) for it in items]
-        names = {torch.uint8: "u8", torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32"}
-        if encoding != "onehot":
+        names = {torch.uint8: "u8", torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32", torch.int32: "i32"}
+        if encoding == "origin":
+            dtype = torch.int32 if dtype is None else dtype
+            if dtype != torch.int32:
+                raise ValueError("'origin' is int32")
+        elif encoding != "onehot":
             dtype = torch.uint8 if dtype is None else dtype
             if dtype != torch.uint8:
                 raise ValueError(f"{encoding!r} is uint8")

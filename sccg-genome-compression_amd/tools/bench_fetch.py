@@ -19,7 +19,12 @@ one-hot f16, interleaved call by call: (a) one sccg_cohort_fetch_device, (b) S
 sccg_reader_fetch_encoded_device calls of the same regions grouped by sample, (c) the same total
 shape from one reader in one call, and (a1) the cohort call over ONE reader listed S times, which
 keeps (a)'s per-span descriptor reads and (c)'s memory footprint; with the readers' device bytes and
-open times, private against shared.  Every shape's bytes are checked against the target FASTA.  Prints one JSON line
+open times, private against shared.  Then the origin fetch (SCCG_ENC_ORIGIN, 4 bytes per base, R' never
+read) beside index (1 byte) and one-hot u8 (the same 4 bytes, R' read) at the same two shapes, one
+reader and the S-sample cohort, all through a reference opened with SCCG_REF_COORDS and interleaved
+call by call; and sccg_reference_open_device with and without SCCG_REF_COORDS.  --only-origin runs
+that last section alone.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
+must name the reference base the target's base is, -2 an N).  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
 import ctypes
@@ -146,6 +151,109 @@ def cohort_section(a, ctx, lib, torch, sccg, dev, stream, rd, d_ref, ref_len, d_
     return out
 
 
+def origin_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, rec_len, truth, rfa, code, S=8):
+    """Reference open with and without the R' -> R map; index / one-hot u8 / origin, reader and cohort."""
+    s = stream.cuda_stream
+    out = {"samples": S, "same_record": True}
+
+    def opened(coords):
+        ts, h = [], None
+        for _ in range(3):
+            if h is not None:
+                h.close()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            h = ctx.open_reference_device(d_ref.data_ptr(), ref_len, stream=s, coords=coords)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return h, spread(ts)
+
+    plain, out["reference_open_ms"] = opened(False)
+    ref, out["reference_open_coords_ms"] = opened(True)
+    out["reference_device_bytes"] = {"plain": plain.device_bytes, "coords": ref.device_bytes}
+    plain.close()
+    readers = [ref.open_reader_device(d_rec.data_ptr(), rec_len, s) for _ in range(S)]
+    rd, co = readers[0], sccg.Cohort(readers)
+    L = rd.length
+    Ru = np.frombuffer(rfa.partition(b"\n")[2].replace(b"\n", b"").upper(), dtype=np.uint8)
+    Tu = np.frombuffer(truth.upper(), dtype=np.uint8)
+    codes = np.array(code, dtype=np.uint8)
+    rng = random.Random(3)
+    out["fetch"] = {}
+    rows = {"index": ("index", "u8", 1), "onehot_u8": ("onehot", "u8", 4), "origin": ("origin", "i32", 4)}
+    for name, (n, ln) in {"1000x1kb": (1000, 1000), "100000x100b": (100_000, 100)}.items():
+        begins = [rng.randrange(L - ln) for _ in range(n)]
+        samp = [k % S for k in range(n)]
+        rng.shuffle(samp)
+        F = n * ln
+        items = (sccg.CohortRegion * n)(*[(b, b + ln, sm, 0) for b, sm in zip(begins, samp)])
+        flat = (sccg.Region * n)(*[(b, b + ln) for b in begins])
+        pos = (np.array(begins, dtype=np.int64)[:, None] + np.arange(ln, dtype=np.int64)[None, :]).reshape(-1)
+        got = ctypes.c_size_t()
+        calls, bufs = {}, {}
+        for row, (enc, dt, bpb) in rows.items():
+            fmt = sccg.FetchFormat(sccg.ENCODINGS[enc], sccg.DTYPES[dt], 0, 0)
+            for who in ("reader", "cohort"):
+                d_o = torch.empty(F * bpb + 64, dtype=torch.uint8, device=dev)
+                bufs[f"{row}/{who}"] = (d_o, bpb)
+
+                def call(fmt=fmt, d_o=d_o, bpb=bpb, who=who):
+                    if who == "reader":
+                        rc = lib.sccg_reader_fetch_encoded_device(rd.ptr, flat, n, None, ctypes.byref(fmt), d_o.data_ptr(), F * bpb,
+                                                                  ctypes.byref(got), s)
+                    else:
+                        rc = lib.sccg_cohort_fetch_device(co.ptr, items, n, ctypes.byref(fmt), d_o.data_ptr(), F * bpb,
+                                                          ctypes.byref(got), s)
+                    assert rc == 0 and got.value == F * bpb, (rc, got.value)
+
+                calls[f"{row}/{who}"] = call
+        ev = {k: [] for k in calls}
+        for i in range(a.warmup + a.calls):   # interleaved: every leg once per round
+            for k, call in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                stream.synchronize()
+                e0.record(stream)
+                call()
+                e1.record(stream)
+                stream.synchronize()
+                if i >= a.warmup:
+                    ev[k].append(e0.elapsed_time(e1))
+        kern = {}
+        for k, call in calls.items():
+            ctx.profile(True, families=["fetch"])
+            for _ in range(a.calls):
+                call()
+            t = ctx.profile_get().get("fetch", (0.0, 0))
+            ctx.profile(False)
+            kern[k] = (round(t[0] / max(t[1], 1), 4), t[1] / a.calls)
+        c = codes[Tu[pos]]
+        for k, (d_o, bpb) in bufs.items():
+            raw = d_o[:F * bpb].cpu().numpy()
+            if k.startswith("index"):
+                exact = bool(np.array_equal(raw, c))
+            elif k.startswith("onehot"):
+                exact = bool(np.array_equal(raw.reshape(-1, 4), np.vstack([np.eye(4, dtype=np.uint8), np.zeros((1, 4), dtype=np.uint8)])[c]))
+            else:
+                o = raw.view("<i4")
+                cop = o >= 0
+                exact = bool(o.min() >= -2 and o.max() < len(Ru) and np.array_equal(Ru[o[cop]], Tu[pos][cop])
+                             and np.all(Tu[pos][o == -2] == ord("N")))
+                out["fetch"].setdefault(f"{name}/shares", {"copied": round(float(cop.mean()), 4), "literal": round(float((o == -1).mean()), 4),
+                                                           "n_run": round(float((o == -2).mean()), 4)})
+            med = statistics.median(ev[k])
+            out["fetch"][f"{name}/{k}"] = {"bytes": F * bpb, "event_ms": spread(ev[k]), "kernel_ms_mean": kern[k][0],
+                                           "launches_per_call": kern[k][1], "out_GBps": round(F * bpb / med / 1e6, 1), "exact": exact}
+        for who in ("reader", "cohort"):
+            m = {row: statistics.median(ev[f"{row}/{who}"]) for row in rows}
+            out["fetch"][f"{name}/{who}/origin_over_onehot_u8"] = round(m["origin"] / m["onehot_u8"], 3)
+        bufs.clear()
+        calls.clear()
+    co.close()
+    for r in readers:
+        r.close()
+    ref.close()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", default="hg")
@@ -154,6 +262,7 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--only-origin", action="store_true", help="the origin section alone")
     a = ap.parse_args()
     import torch
     import sccg
@@ -186,6 +295,18 @@ def main() -> None:
                 ev.append(e0.elapsed_time(e1))
                 host.append((t1 - t0) * 1e3)
         return ev, host
+
+    code = [4] * 256
+    for k, ch in enumerate(b"ACGT"):
+        code[ch] = code[ch + 32] = k
+    if a.only_origin:
+        out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
+               "origin": origin_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth, rfa, code)}
+        ctx.close()
+        print(json.dumps(out))
+        if not all(v["exact"] for v in out["origin"]["fetch"].values() if isinstance(v, dict) and "exact" in v):
+            raise SystemExit("bench_fetch: origin section: bytes differ from the target FASTA")
+        return
 
     # ---- yardstick: the full reconstruction
     need = ctx.reconstruct_device(d_ref.data_ptr(), len(rfa), d_rec.data_ptr(), len(rec_h), 0, 0, s)
@@ -307,9 +428,13 @@ def main() -> None:
         del d_a
     if hasattr(lib, "sccg_cohort_fetch_device"):   # (absent from a library older than the cohort fetch)
         out["cohort"] = cohort_section(a, ctx, lib, torch, sccg, dev, stream, rd, d_ref, len(rfa), d_rec, len(rec_h), truth, code)
+    if hasattr(lib, "sccg_reader_has_coords"):   # (absent from a library older than the origin fetch)
+        out["origin"] = origin_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth, rfa, code)
     rd.close()
     ctx.close()
     print(json.dumps(out))
+    if "origin" in out and not all(v["exact"] for v in out["origin"]["fetch"].values() if isinstance(v, dict) and "exact" in v):
+        raise SystemExit("bench_fetch: origin section: bytes differ from the target FASTA")
     if "cohort" in out and not all(v["exact"] for v in out["cohort"]["fetch"].values()):
         raise SystemExit("bench_fetch: cohort bytes differ from the target FASTA")
     if not all(v["exact"] and v["two_step_exact"] for v in out["fetch_encoded"].values()):
