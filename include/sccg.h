@@ -164,7 +164,8 @@ int sccg_compress_files(sccg_ctx* ctx, const sccg_params* params, const char* re
 /* match_sequences(Sr, St, k, m, global, offset) on already-uppercased byte strings.  Accepted
  * shapes: global == 0 with |Sr| <= 1000 and |St| <= 1000 (the local-segment kernel), or
  * global == 1 with 0 <= m <= 127 and 1 <= k <= 32 (the windowed global walk).  Others:
- * SCCG_E_UNSUPPORTED. */
+ * SCCG_E_UNSUPPORTED.  A global call sets sccg_last_stats' walk fields (n_matches, walk_rounds,
+ * walk_chunks, target_bases, walk_reference_bases) as sccg_walk_range does. */
 int sccg_match(sccg_ctx* ctx, const uint8_t* sr, size_t nr, const uint8_t* st, size_t nt, int k,
                int m, int global, int64_t offset, sccg_records* out);
 void sccg_records_free(sccg_records* r);

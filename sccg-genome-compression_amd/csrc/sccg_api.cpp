@@ -2353,6 +2353,14 @@ int sccg_match(sccg_ctx* ctx, const uint8_t* sr, size_t nr, const uint8_t* st, s
             prev_end = ht[i] + hl[i];
         }
         if ((int64_t)nt > prev_end) push(0, 0, (int32_t)((int64_t)nt - prev_end), prev_end);
+        // (as sccg_walk_range: the walk's own counters, so a caller can tell how the seam ran)
+        ctx->stats = sccg_stats{};
+        ctx->stats.mode_global = 1;
+        ctx->stats.n_matches = nm;
+        ctx->stats.walk_rounds = wr.rounds;
+        ctx->stats.walk_chunks = wr.chunks;
+        ctx->stats.target_bases = (int64_t)nt;
+        ctx->stats.walk_reference_bases = (int64_t)nr;
     }
     const size_t n = kind.size();
     out->n = (int64_t)n;

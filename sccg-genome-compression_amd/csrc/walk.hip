@@ -812,7 +812,10 @@ void k_walk(WalkPtrs A, const int32_t* __restrict__ list, int32_t nlist, const i
         if (p == 0) {   // pn2 == 0: the reference falls back to the ungated (pn1, ln1) (:134-138)
             escalated = true;
             if (lane == 0 && !CARRY) {   // (a carried chunk is left as it was: pending next round)
-                if (kind == KIND_SPEC) { KC->cnt[ob][j] = 0; KC->exitX[j] = INVALID; KC->exitP[j] = INVALID; }
+                // (speculative: the trajectory is thrown away, and so is the entry it was walked from --
+                // a guess that IS the predecessor's exit, as a trapped trigger's P often is, would
+                // otherwise pass the pending check and settle the chunk with no trajectory and no exit)
+                if (kind == KIND_SPEC) { KC->cnt[ob][j] = 0; KC->exitX[j] = INVALID; KC->exitP[j] = INVALID; KC->usedP[j] = INVALID; }
                 else {
                     KC->status[j] = ST_ESC;
                     KC->escX[j] = y; KC->escP[j] = P; KC->escN[j] = n; KC->escQ[j] = q;
