@@ -73,36 +73,38 @@ struct DcFetchSrc {
     DcRuns nr, lr;
     DcRuns rm;
 };
-// d_out[0, F) = the sequence bytes of regions [d_beg[i], d_beg[i] + d_pre[i + 1] - d_pre[i]), i < nreg,
-// concatenated (d_pre: exclusive prefix of the lengths, d_pre[nreg] = F); upper: no lowercase runs.
-// One launch whatever nreg is; regions and tokens were validated by the caller.
-int dc_fetch(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, bool upper,
-             uint8_t* d_out, hipStream_t s);
-// The same regions encoded (enc: SCCG_ENC_*, dt: SCCG_DT_*, a valid pair): d_out[0, bytes_per_base * F),
-// base-major.  Region i is on the reverse strand (position end - 1 - q at output base q, complemented)
-// when bit 63 of d_beg[i] is set or all_rev; upper matters for ASCII only.  d_out aligned to the
-// element size.  One launch, under the same profiler family as dc_fetch.
-int dc_fetch_encoded(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, int enc, int dt,
-                     bool upper, bool all_rev, uint8_t* d_out, hipStream_t s);
-
-// A cohort's device table (sccg_cohort_create): one entry per sample, the reader's source and what
-// k_fetch_enc hoists per launch (nn = S.nr.n, nlr = S.lr.n, ntot = the N bases of the sequence).
+// A source as the fetch kernels take it: with what they would otherwise derive per launch (nn =
+// S.nr.n, nlr = S.lr.n, ntot = the N bases of the sequence).  A cohort's device table
+// (sccg_cohort_create) holds one per sample.
 struct DcCohortEntry {
     DcFetchSrc S;
     int64_t nn, nlr, ntot;
 };
-// dc_fetch_encoded with the source chosen per region: region i reads d_tab[d_samp[i]] (every index
-// validated by the caller, as the regions are).  One launch, under the same profiler family.
-int dc_fetch_cohort(const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg, const int32_t* d_samp, int64_t nreg,
-                    int64_t F, int enc, int dt, bool upper, bool all_rev, uint8_t* d_out, hipStream_t s);
-
-// Origin fetch (SCCG_ENC_ORIGIN): d_out[0, F) int32, one per base of the same flat space -- the
-// position in the reference sequence a token copied the base from (R' positions through S.rm), -1 for
-// a literal, -2 inside one of the target's N runs; a reversed region's values come in reverse order,
-// unchanged.  src given: the reader's source (d_tab, d_samp unused); src null: region i reads
-// d_tab[d_samp[i]].  d_out 4-byte aligned.  One launch, under the fetch profiler family; R' is not read.
-int dc_fetch_origin(const DcFetchSrc* src, const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg,
-                    const int32_t* d_samp, int64_t nreg, int64_t F, bool all_rev, int32_t* d_out, hipStream_t s);
+// One fetch: d_out[0, bytes per base * F), base-major, the bases of regions [d_beg[i], d_beg[i] +
+// d_pre[i + 1] - d_pre[i]), i < nreg, concatenated (d_pre: exclusive prefix of the lengths,
+// d_pre[nreg] = F).  src given: all from that reader (d_tab, d_samp unused); src null: region i reads
+// d_tab[d_samp[i]].  Region i is on the reverse strand (position end - 1 - q at output base q) when bit
+// 63 of d_beg[i] is set or all_rev.  The format (enc: SCCG_ENC_*, dt: SCCG_DT_*, a valid pair):
+//   ASCII / INDEX / ONEHOT  the sequence byte, its code, its one-hot elements (complemented when
+//                           reversed); upper (no lowercase runs) matters for ASCII only
+//   ORIGIN (I32)            the position in the reference sequence a token copied the base from (R'
+//                           positions through S.rm; R' is not read), -1 for a literal, -2 inside one of
+//                           the target's N runs; unchanged on the reverse strand
+// (sccg_reader_fetch's bytes are ASCII with no region reversed.)  d_out is aligned to the element.
+// Regions, samples and tokens were validated by the caller.
+struct DcFetch {
+    const DcFetchSrc* src;
+    const DcCohortEntry* d_tab;
+    const int64_t* d_pre;
+    const int64_t* d_beg;
+    const int32_t* d_samp;
+    int64_t nreg, F;
+    int enc, dt;
+    bool upper, all_rev;
+    void* d_out;
+};
+// One launch whatever nreg and the samples touched are, under the profiler's fetch family.
+int dc_fetch(const DcFetch& c, hipStream_t s);
 
 // The R' -> R map: the maximal runs of the byte 'N' in the stripped, original-case reference d_R[0, n)
 // (n < 2^31, 16-byte aligned, 16 readable bytes behind it).  dc_refmap_count: d_nruns[0] = the runs

@@ -923,17 +923,23 @@ __global__ __launch_bounds__(256) void k_format_out(const uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Region fetch (sccg_reader_fetch): bytes [begin, end) of the sequence -- result of
-// decompression.cpp:241-262, N inserted and lowercased, no '\n' -- for a batch of regions,
+// Region fetch (sccg_reader_fetch*, sccg_cohort_fetch*): bases [begin, end) of the sequence -- result
+// of decompression.cpp:241-262, N inserted and lowercased, no '\n' -- for a batch of regions,
 // concatenated in the order given, from the state a reader keeps (DcFetchSrc).  One launch for the
-// whole batch.  The flat output is tiled as in the formatter: a block owns OB bytes of it, 16-byte
-// aligned in memory, a wave FT_W = 1 KiB of those, a lane 16.  A wave finds its first region in the
-// prefix of region lengths and then takes the spans [j0, j1) of sequence positions its bytes cover
-// one after the other.  Per span: positions -> decoded offsets [d0, d1) over the N runs, decoded
-// offsets -> record blocks [b0, b1] over boff, the k_tok_fill2 parse of just those blocks with
-// every literal and token copy clipped to [d0, d1) into the wave's LDS tile (a long token is entered
-// at R' + p + (d0 - o)), then the formatter's per-byte N / lowercase walk over the tile.  Every
-// search is a wave-wide 64-ary one (64 probes per step); nothing is swept end to end, no scratch
+// whole batch.  The flat space of output bases is tiled as in the formatter: a block owns OB of
+// them, a wave FT_W = 1,024, a lane 16, 16-byte pieces aligned in memory.  The parts, in this order:
+//   fetch_decode_span  a span's decode: positions [j0, j1) -> decoded offsets [d0, d1) over the N
+//                      runs -> record blocks [b0, b1] over boff -> the k_tok_fill2 parse of just those
+//                      blocks, every literal and token copy clipped to [d0, d1), into the wave's LDS
+//                      tile (a long token is entered at R' + p + (d0 - o)); ORIGIN keeps where a byte
+//                      comes from instead of the byte
+//   NCursor, LCursor   a lane's cursors over the N and the lowercase runs for the formatter's
+//                      per-base walk over that tile
+//   fetch_spans        the loop every kernel sits on: the wave's first region in the prefix of region
+//                      lengths, then its spans one after the other, each with its source and strand
+//   k_fetch_enc        bytes, codes or one-hot elements; k_fetch_origin: reference positions
+//   dc_fetch           the one launcher
+// Every search is a wave-wide 64-ary one (64 probes per step); nothing is swept end to end, no scratch
 // beyond LDS.  The reader's open has checked every token and run: nothing is re-checked here.
 // ---------------------------------------------------------------------------------------------
 constexpr int FT_W = 64 * OPT;
@@ -1124,87 +1130,145 @@ __device__ __forceinline__ FetchSpan fetch_decode_span(const DcFetchSrc& S, int6
     return FetchSpan{rn0, d0};
 }
 
+// A lane's cursor over the N runs while its positions j ascend: run r is [s, e) with b N bases before
+// it; past the last run s = e = INT64_MAX and b = ntot.  (The run pointers stay plain: __restrict__
+// here cost the ASCII kernel 4 VGPRs.)
+struct NCursor {
+    const int32_t* ns;
+    const int32_t* nl;
+    const int64_t* ncum;
+    int64_t nn, ntot, r, s, e, b;
+    __device__ __forceinline__ NCursor(const DcCohortEntry& E, int64_t r0)
+        : ns(E.S.nr.start), nl(E.S.nr.len), ncum(E.S.nr.cum), nn(E.nn), ntot(E.ntot), r(r0) {
+        load();
+    }
+    __device__ __forceinline__ void load() {   // (the sentinel first: as an else arm it put ntot on the stack)
+        s = e = INT64_MAX;
+        b = ntot;
+        if (r < nn) { s = ns[r]; e = s + nl[r]; b = ncum[r]; }
+    }
+    __device__ __forceinline__ void seek(int64_t j) {   // the first run ending after j
+        while (j >= e) {
+            r++;
+            load();
+        }
+    }
+};
+// The same over the first nlr lowercase runs (nlr == 0: case is not looked at).
+struct LCursor {
+    const int32_t* ls;
+    const int32_t* ll;
+    int64_t nlr, r, s, e;
+    __device__ __forceinline__ LCursor(const DcCohortEntry& E, int64_t nlr_, int64_t r0)
+        : ls(E.S.lr.start), ll(E.S.lr.len), nlr(nlr_), r(r0) {
+        load();
+    }
+    __device__ __forceinline__ void load() {
+        s = e = INT64_MAX;
+        if (r < nlr) { s = ls[r]; e = s + ll[r]; }
+    }
+    __device__ __forceinline__ void seek(int64_t j) {
+        while (j >= e) {
+            r++;
+            load();
+        }
+    }
+};
+// the first lowercase run (of the nlr looked at) ending after j0: the LCursor's start, wave-wide
+__device__ __forceinline__ int64_t first_lower_run(const DcCohortEntry& E, int64_t nlr, int64_t j0) {
+    const int32_t* __restrict__ ls = E.S.lr.start;
+    const int32_t* __restrict__ ll = E.S.lr.len;
+    return wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
+}
+
+// What every fetch kernel is launched with (dc_fetch fills it).  The flat space is counted in bases:
+// block 0's first base is o_first <= 0, so that a wave's 16-byte pieces are aligned in memory.
 struct FetchArgs {
-    DcFetchSrc S;
-    const int64_t* pre;   // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
-    const int64_t* beg;   // nreg: region begins
-    int64_t nreg, F, o_first, nlr;   // nlr: lowercase runs looked at (0 with SCCG_FETCH_UPPER)
-    uint8_t* out;
+    DcCohortEntry E;            // the reader's source (!COHORT)
+    const DcCohortEntry* tab;   // one entry per sample (COHORT)
+    const int64_t* pre;         // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
+    const int64_t* beg;         // nreg: region begins, bit 63 set = reverse strand
+    const int32_t* samp;        // nreg: region samples (COHORT)
+    int64_t nreg, F, o_first;
+    uint32_t all_rev, elemwise, upper;   // elemwise: out is not on a base boundary; upper: no lowercase runs
+    void* out;
 };
 
-__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch(const FetchArgs A) {
-    __shared__ uint8_t tile[WPB][FT_W];
-    __shared__ uint8_t stg[WPB][2 * TK_B];
-    const int lane = lane_id();
-    uint8_t* sdec = tile[wave_in_block()];
-    uint8_t* st = stg[wave_in_block()];
+// A table entry through a wave-uniform index, read as constant memory (nothing writes the table
+// after sccg_cohort_create): with both, the loads are scalar and the entry lands in SGPRs, as the
+// reader's entry in the kernel arguments does.
+typedef const int64_t __attribute__((address_space(4))) * ConstWords;
+__device__ __forceinline__ DcCohortEntry cohort_entry(const DcCohortEntry* tab, int sm) {
+    constexpr int NW = (int)(sizeof(DcCohortEntry) / sizeof(int64_t));
+    static_assert(sizeof(DcCohortEntry) == NW * sizeof(int64_t), "an entry is whole 8-byte words");
+    const ConstWords w = (ConstWords)(uintptr_t)(tab + sm);
+    int64_t v[NW];
+#pragma unroll
+    for (int k = 0; k < NW; k++) v[k] = w[k];
+    DcCohortEntry E;
+    __builtin_memcpy(&E, v, sizeof E);
+    return E;
+}
+
+// The wave's tile of the flat space: bases [base, base + FT_W), of which [w0, fend) are this launch's
+// (none when w0 >= fend); lane l owns the OPT bases from base + l * OPT.
+struct FetchTile {
+    int64_t base, w0, fend;
+};
+__device__ __forceinline__ FetchTile fetch_tile(const FetchArgs& A) {
     const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
-    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
-    int64_t f = base < 0 ? 0 : base;
-    if (f >= fend) return;
-    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 output bytes
-    const int32_t* __restrict__ ns = A.S.nr.start;
-    const int32_t* __restrict__ nl = A.S.nr.len;
-    const int64_t* __restrict__ ncum = A.S.nr.cum;
-    const int32_t* __restrict__ ls = A.S.lr.start;
-    const int32_t* __restrict__ ll = A.S.lr.len;
-    const int64_t nn = A.S.nr.n, nlr = A.nlr;
-    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
+    return FetchTile{base, base < 0 ? 0 : base, base + FT_W < A.F ? base + FT_W : A.F};
+}
+
+// The loop of every fetch kernel: the spans of the wave's tile one after the other.  It finds the
+// region holding the tile's first base in the prefix (the last i with pre[i] <= f; an empty region
+// never is), steps to the next region that is not empty, takes the span's sample entry -- COHORT:
+// samp[i] made provably uniform (readfirstlane) and, when it differs from the sample held, its table
+// entry; else the entry of the arguments -- and maps the span [f, fe) to the forward positions
+// [j0, j1) it covers (j1 - j0 <= FT_W): a region is reversed by bit 63 of its begin or all_rev, and
+// flat base g of a reversed region is position end - 1 - (g - pre[i]).  The whole wave then calls
+//     body(entry, j0, j1, rev, j, k0, k1)
+// where the lane's bases of the span are its k0-th to k1-th (none: k0 >= k1) and j is the lowest of
+// their positions: the lane walks j ascending and places result t at k0 + t, or k1 - 1 - t when rev.
+// What the body read of the wave's tiles is synchronised before the next span, and once more after
+// the last.
+template <bool COHORT, typename Body>
+__device__ __forceinline__ void fetch_spans(const FetchArgs& A, const FetchTile& T, Body&& body) {
+    const int64_t g0 = T.base + (int64_t)lane_id() * OPT;
     const int64_t* __restrict__ pre = A.pre;
-    // the region holding flat byte f: the last i with pre[i] <= f (an empty region never is)
+    DcCohortEntry E = A.E;
+    int cur = -1;   // the sample E holds (COHORT)
+    int64_t f = T.w0;
     int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-    while (f < fend) {
-        if (pre[i + 1] <= f) {   // the next region that is not empty: usually i + 1, else searched for
+    while (f < T.fend) {
+        if (pre[i + 1] <= f) {   // usually i + 1 is not empty, else searched for
             i++;
             if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
         }
-        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
-        const int64_t j0 = A.beg[i] + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
-        const FetchSpan sp = fetch_decode_span(A.S, j0, j1, sdec, st);
-        const int64_t rn0 = sp.rn0, d0 = sp.d0;
-        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
-        // the lane's bytes of this span: the formatter's per-byte walk over the runs, without the wrap
-        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
-        if (ga < gb) {
-            int64_t j = j0 + (ga - f), rn = rn0, rl = rl0;
-            int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot, l_s = INT64_MAX, l_e = INT64_MAX;
-            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
-            if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
-            uint64_t lo = 0, hi = 0;
-            const int k0 = (int)(ga - g0), k1 = (int)(gb - g0);
-            for (int k = k0; k < k1; k++) {
-                while (j >= n_e) {
-                    rn++;
-                    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
-                    else { n_s = n_e = INT64_MAX; n_b = ntot; }
-                }
-                while (j >= l_e) {
-                    rl++;
-                    if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
-                    else l_s = l_e = INT64_MAX;
-                }
-                uint32_t c = j >= n_s ? (uint32_t)'N' : (uint32_t)sdec[j - n_b - d0];
-                if (j >= l_s) c = c_tolower((uint8_t)c);
-                j++;
-                if (k < 8) lo |= (uint64_t)c << (8 * k);
-                else hi |= (uint64_t)c << (8 * (k - 8));
-            }
-            if (k0 == 0 && k1 == OPT) {
-                store16(A.out + g0, lo, hi);
-            } else {
-                for (int k = k0; k < k1; k++) A.out[g0 + k] = (uint8_t)((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8))) & 0xff);
+        if (COHORT) {
+            const int sm = __builtin_amdgcn_readfirstlane(A.samp[i]);
+            if (sm != cur) {   // (wave-uniform: a scalar branch around scalar loads)
+                cur = sm;
+                E = cohort_entry(A.tab, sm);
             }
         }
+        const int64_t fe = pre[i + 1] < T.fend ? pre[i + 1] : T.fend;
+        const int64_t braw = A.beg[i];
+        const bool rev = A.all_rev || braw < 0;
+        const int64_t bg = braw & INT64_MAX;
+        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);
+        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
+        body(E, j0, j1, rev, rev ? j0 + (fe - gb) : j0 + (ga - f), (int)(ga - g0), (int)(gb - g0));
         wave_sync();   // (the tile is read before the next span fills it)
         f = fe;
     }
+    wave_sync();
 }
 
 // ---------------------------------------------------------------------------------------------
-// Encoded region fetch (sccg_reader_fetch_encoded): k_fetch's flat space counted in BASES -- a wave
-// owns FT_W bases, a block OB -- with the strand and the encoding as an epilogue.  A span of a
-// reversed region (bit 63 of its begin, or all_rev) is mapped to the forward interval [j0, j1) it
-// covers and decoded forward by fetch_decode_span; a lane walks its bases ascending in j and
+// The byte kernels (k_fetch_enc<ENC, DT, COHORT>; sccg_reader_fetch's bytes are ASCII, forward): the
+// strand and the encoding are an epilogue on the decode tile.  Each span is decoded forward by
+// fetch_decode_span; a lane walks its bases ascending in j and
 // writes each final byte (ASCII, complemented when reversed) or code (0-3, 4 = not ACGT; 3 - code
 // when reversed) at its OUTPUT place in a second LDS tile, `fin`, one byte per base.  When the
 // wave's spans are done it streams fin out in 16-byte pieces, piece q to lane q % 64, so every
@@ -1212,10 +1276,10 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch(const FetchArgs A) {
 // piece holds 16 / 4 / 2 / 1 bases at 1 / 4 / 8 / 16 bytes per base, expanded from the codes in
 // registers.  Pieces cut by the tile's ends [max(base, 0), fend), and every piece when d_out is
 // not aligned to a whole base (elemwise), are stored element by element.  INDEX and ONEHOT are
-// case-blind: they are launched with nlr = 0 and never look at the lowercase runs.
+// case-blind: their nlr is 0 and they never look at the lowercase runs.
 // ---------------------------------------------------------------------------------------------
-constexpr int FE_ASCII = 0, FE_INDEX = 1, FE_ONEHOT = 2;     // SCCG_ENC_*
-constexpr int FD_U8 = 0, FD_F16 = 1, FD_BF16 = 2, FD_F32 = 3;   // SCCG_DT_*
+constexpr int FE_ASCII = 0, FE_INDEX = 1, FE_ONEHOT = 2, FE_ORIGIN = 3;      // SCCG_ENC_*
+constexpr int FD_U8 = 0, FD_F16 = 1, FD_BF16 = 2, FD_F32 = 3, FD_I32 = 4;   // SCCG_DT_*
 
 // IUPAC complement of an uppercase letter as its index 0..25, 13 letters x 5 bits per word
 // (A<->T C<->G R<->Y K<->M B<->V D<->H; every other letter is its own)
@@ -1251,32 +1315,20 @@ __device__ __forceinline__ uint32_t base_code(uint32_t c) {
     return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 4u;
 }
 
-// A lane's bases of one span, shared by the encoded fetch kernels: positions j, j + 1, ... (ascending)
-// through the N runs from rn and the lowercase runs from rl, each final byte or code at its output
-// place mine[k0, k1) -- descending for a reversed span.
+// A lane's bases of one span (fetch_spans' j, k0, k1): positions j, j + 1, ... through the N runs
+// from rn and the lowercase runs from rl, each final byte or code at its output place in
+// mine[k0, k1) -- descending for a reversed span.
 template <int ENC>
-__device__ __forceinline__ void fetch_enc_walk(const int32_t* ns, const int32_t* nl,
-                                               const int64_t* ncum, const int32_t* ls,
-                                               const int32_t* ll, int64_t nn, int64_t nlr, int64_t ntot,
-                                               const uint8_t* sdec, uint8_t* mine, int64_t j, int64_t rn, int64_t rl, int64_t d0,
-                                               bool rev, int k0, int k1) {
-    int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot, l_s = INT64_MAX, l_e = INT64_MAX;
-    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
-    if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
+__device__ __forceinline__ void fetch_enc_walk(const DcCohortEntry& E, int64_t nlr, const uint8_t* sdec, uint8_t* mine, int64_t j,
+                                               int64_t rn, int64_t rl, int64_t d0, bool rev, int k0, int k1) {
+    NCursor N(E, rn);
+    LCursor L(E, nlr, rl);
     for (int t = 0; t < k1 - k0; t++) {
-        while (j >= n_e) {
-            rn++;
-            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
-            else { n_s = n_e = INT64_MAX; n_b = ntot; }
-        }
-        while (j >= l_e) {
-            rl++;
-            if (rl < nlr) { l_s = ls[rl]; l_e = l_s + ll[rl]; }
-            else l_s = l_e = INT64_MAX;
-        }
-        uint32_t c = j >= n_s ? (uint32_t)'N' : (uint32_t)sdec[j - n_b - d0];
+        N.seek(j);
+        L.seek(j);
+        uint32_t c = j >= N.s ? (uint32_t)'N' : (uint32_t)sdec[j - N.b - d0];
         if (ENC == FE_ASCII) {
-            if (j >= l_s) c = c_tolower((uint8_t)c);
+            if (j >= L.s) c = c_tolower((uint8_t)c);
             if (rev) c = comp_ascii(c);
         } else {
             c = base_code(c);
@@ -1347,17 +1399,8 @@ __device__ __forceinline__ void fetch_enc_stream(const uint8_t* fw, int64_t base
     }
 }
 
-struct FetchEncArgs {
-    DcFetchSrc S;
-    const int64_t* pre;   // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
-    const int64_t* beg;   // nreg: region begins, bit 63 set = reverse strand
-    int64_t nreg, F, o_first, nlr;   // o_first: the flat base of block 0's first base (<= 0)
-    uint32_t all_rev, elemwise;
-    uint8_t* out;
-};
-
-template <int ENC, int DT>
-__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_enc(const FetchEncArgs A) {
+template <int ENC, int DT, bool COHORT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_enc(const FetchArgs A) {
     static_assert(ENC == FE_ONEHOT || DT == FD_U8, "ASCII and INDEX are bytes");
     __shared__ uint8_t tile[WPB][FT_W];
     __shared__ __attribute__((aligned(16))) uint8_t fin[WPB][FT_W];
@@ -1366,139 +1409,16 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_enc(const FetchEncArgs A) 
     uint8_t* sdec = tile[wave_in_block()];
     uint8_t* fw = fin[wave_in_block()];
     uint8_t* st = stg[wave_in_block()];
-    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
-    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
-    const int64_t w0 = base < 0 ? 0 : base;
-    int64_t f = w0;
-    if (f >= fend) return;
-    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
-    const int32_t* __restrict__ ns = A.S.nr.start;
-    const int32_t* __restrict__ nl = A.S.nr.len;
-    const int64_t* __restrict__ ncum = A.S.nr.cum;
-    const int32_t* __restrict__ ls = A.S.lr.start;
-    const int32_t* __restrict__ ll = A.S.lr.len;
-    const int64_t nn = A.S.nr.n, nlr = ENC == FE_ASCII ? A.nlr : 0;
-    const int64_t ntot = nn ? ncum[nn - 1] + nl[nn - 1] : 0;
-    const int64_t* __restrict__ pre = A.pre;
-    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-    while (f < fend) {
-        if (pre[i + 1] <= f) {
-            i++;
-            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-        }
-        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
-        const int64_t braw = A.beg[i];
-        const bool rev = A.all_rev || braw < 0;
-        const int64_t bg = braw & INT64_MAX;
-        // reversed: flat base g of the region is position end - 1 - (g - pre[i]); [f, fe) covers [j0, j1)
-        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
-        const FetchSpan sp = fetch_decode_span(A.S, j0, j1, sdec, st);
-        const int64_t rn0 = sp.rn0, d0 = sp.d0;
-        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
-        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
-        if (ga < gb) {
-            // ascending in j; a reversed span's results land at descending places
-            const int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f);
-            fetch_enc_walk<ENC>(ns, nl, ncum, ls, ll, nn, nlr, ntot, sdec, fw + lane * OPT, j, rn0, rl0, d0, rev, (int)(ga - g0),
-                                (int)(gb - g0));
-        }
-        wave_sync();   // (the tile is read before the next span fills it)
-        f = fe;
-    }
-    wave_sync();   // fin[w0 - base, fend - base) is complete
-    fetch_enc_stream<ENC, DT>(fw, base, w0, fend, A.elemwise, A.out, lane);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Cohort fetch (sccg_cohort_fetch): k_fetch_enc with the source chosen per SPAN, not per launch.
-// Region i names its sample in samp[i]; the wave makes the index provably uniform (readfirstlane)
-// and reads that sample's entry of the cohort's table through a uniform address, so the entry
-// arrives by scalar loads and lives in SGPRs as k_fetch_enc's kernel arguments do.  The entry is
-// kept while consecutive spans stay on one sample.  What k_fetch_enc hoists per launch (the run
-// lists' pointers and counts, ntot) is per-span state here, taken from the entry.
-// ---------------------------------------------------------------------------------------------
-struct FetchCohortArgs {
-    const DcCohortEntry* tab;   // one entry per sample
-    const int64_t* pre;         // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
-    const int64_t* beg;         // nreg: region begins, bit 63 set = reverse strand
-    const int32_t* samp;        // nreg: region samples
-    int64_t nreg, F, o_first;
-    uint32_t all_rev, elemwise, upper;
-    uint8_t* out;
-};
-
-// A table entry through a wave-uniform index, read as constant memory (nothing writes the table
-// after sccg_cohort_create): with both, the loads are scalar and the entry lands in SGPRs.
-typedef const int64_t __attribute__((address_space(4))) * ConstWords;
-__device__ __forceinline__ DcCohortEntry cohort_entry(const DcCohortEntry* tab, int sm) {
-    constexpr int NW = (int)(sizeof(DcCohortEntry) / sizeof(int64_t));
-    static_assert(sizeof(DcCohortEntry) == NW * sizeof(int64_t), "an entry is whole 8-byte words");
-    const ConstWords w = (ConstWords)(uintptr_t)(tab + sm);
-    int64_t v[NW];
-#pragma unroll
-    for (int k = 0; k < NW; k++) v[k] = w[k];
-    DcCohortEntry E;
-    __builtin_memcpy(&E, v, sizeof E);
-    return E;
-}
-
-template <int ENC, int DT>
-__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_cohort(const FetchCohortArgs A) {
-    static_assert(ENC == FE_ONEHOT || DT == FD_U8, "ASCII and INDEX are bytes");
-    __shared__ uint8_t tile[WPB][FT_W];
-    __shared__ __attribute__((aligned(16))) uint8_t fin[WPB][FT_W];
-    __shared__ uint8_t stg[WPB][2 * TK_B];
-    const int lane = lane_id();
-    uint8_t* sdec = tile[wave_in_block()];
-    uint8_t* fw = fin[wave_in_block()];
-    uint8_t* st = stg[wave_in_block()];
-    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
-    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
-    const int64_t w0 = base < 0 ? 0 : base;
-    int64_t f = w0;
-    if (f >= fend) return;
-    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
-    const DcCohortEntry* __restrict__ tab = A.tab;
-    const int64_t* __restrict__ pre = A.pre;
-    const int32_t* __restrict__ samp = A.samp;
-    DcCohortEntry E{};   // the current span's sample
-    int cur = -1;
-    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-    while (f < fend) {
-        if (pre[i + 1] <= f) {
-            i++;
-            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-        }
-        const int sm = __builtin_amdgcn_readfirstlane(samp[i]);
-        if (sm != cur) {   // (wave-uniform: a scalar branch around scalar loads)
-            cur = sm;
-            E = cohort_entry(tab, sm);
-        }
-        const int32_t* __restrict__ ns = E.S.nr.start;
-        const int32_t* __restrict__ nl = E.S.nr.len;
-        const int64_t* __restrict__ ncum = E.S.nr.cum;
-        const int32_t* __restrict__ ls = E.S.lr.start;
-        const int32_t* __restrict__ ll = E.S.lr.len;
-        const int64_t nn = E.nn, nlr = ENC == FE_ASCII && !A.upper ? E.nlr : 0, ntot = E.ntot;
-        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
-        const int64_t braw = A.beg[i];
-        const bool rev = A.all_rev || braw < 0;
-        const int64_t bg = braw & INT64_MAX;
-        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
+    const FetchTile T = fetch_tile(A);
+    if (T.w0 >= T.fend) return;
+    fetch_spans<COHORT>(A, T, [&](const DcCohortEntry& E, int64_t j0, int64_t j1, bool rev, int64_t j, int k0, int k1) {
         const FetchSpan sp = fetch_decode_span(E.S, j0, j1, sdec, st);
-        const int64_t rn0 = sp.rn0, d0 = sp.d0;
-        const int64_t rl0 = wave_first(0, nlr, [&](int64_t m) { return (int64_t)ls[m] + ll[m] > j0; });
-        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
-        if (ga < gb) {
-            const int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f);
-            fetch_enc_walk<ENC>(ns, nl, ncum, ls, ll, nn, nlr, ntot, sdec, fw + lane * OPT, j, rn0, rl0, d0, rev, (int)(ga - g0),
-                                (int)(gb - g0));
-        }
-        wave_sync();   // (the tile is read before the next span fills it)
-        f = fe;
-    }
-    wave_sync();   // fin[w0 - base, fend - base) is complete
-    fetch_enc_stream<ENC, DT>(fw, base, w0, fend, A.elemwise, A.out, lane);
+        const int64_t nlr = ENC == FE_ASCII && !A.upper ? E.nlr : 0;
+        const int64_t rl0 = first_lower_run(E, nlr, j0);
+        if (k0 < k1) fetch_enc_walk<ENC>(E, nlr, sdec, fw + lane * OPT, j, sp.rn0, rl0, sp.d0, rev, k0, k1);
+    });
+    // fin[w0 - base, fend - base) is complete
+    fetch_enc_stream<ENC, DT>(fw, T.base, T.w0, T.fend, A.elemwise, reinterpret_cast<uint8_t*>(A.out), lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1509,46 +1429,26 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_cohort(const FetchCohortAr
 // token piece (origin_piece); R' itself is never loaded.  A lane walks its bases through the target's
 // N runs as fetch_enc_walk does and places each value.  The finished tile streams out as
 // k_fetch_enc's does: 16-byte pieces of 4 bases, piece q to lane q % 64, element stores for the
-// pieces the tile's ends cut.  One kernel for the reader (the source in the arguments) and the
-// cohort (COHORT: the source of each span from the table, as in k_fetch_cohort).
+// pieces the tile's ends cut.
 // LDS per block: WPB x (2 x FO_TILE x 4 + 2 x TK_B) = 35,328 bytes -> 4 blocks of a CU's 160 KiB,
 // 16 waves per CU, 4 per SIMD.
 // ---------------------------------------------------------------------------------------------
-struct FetchOriginArgs {
-    DcCohortEntry E;            // the reader's source (!COHORT)
-    const DcCohortEntry* tab;   // one entry per sample (COHORT)
-    const int64_t* pre;         // nreg + 1: exclusive prefix of the region lengths, pre[nreg] = F
-    const int64_t* beg;         // nreg: region begins, bit 63 set = reverse strand
-    const int32_t* samp;        // nreg: region samples (COHORT)
-    int64_t nreg, F, o_first;   // o_first: the flat base of block 0's first base (<= 0)
-    uint32_t all_rev;
-    int32_t* out;
-};
-
 // A lane's bases of one span: positions j, j + 1, ... through the target's N runs from rn, each
 // origin at its output place mine[k0, k1) (opad'ed from the lane's first entry m0) -- descending for
 // a reversed span; the value itself is the same on either strand.
-__device__ __forceinline__ void fetch_origin_walk(const DcFetchSrc& S, int64_t nn, int64_t ntot, const int32_t* org, int32_t* fw,
-                                                  int m0, int64_t j, int64_t rn, int64_t d0, bool rev, int k0, int k1) {
-    const int32_t* __restrict__ ns = S.nr.start;
-    const int32_t* __restrict__ nl = S.nr.len;
-    const int64_t* __restrict__ ncum = S.nr.cum;
-    int64_t n_s = INT64_MAX, n_e = INT64_MAX, n_b = ntot;
-    if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
+__device__ __forceinline__ void fetch_origin_walk(const DcCohortEntry& E, const int32_t* org, int32_t* fw, int m0, int64_t j,
+                                                  int64_t rn, int64_t d0, bool rev, int k0, int k1) {
+    NCursor N(E, rn);
     for (int t = 0; t < k1 - k0; t++) {
-        while (j >= n_e) {
-            rn++;
-            if (rn < nn) { n_s = ns[rn]; n_e = n_s + nl[rn]; n_b = ncum[rn]; }
-            else { n_s = n_e = INT64_MAX; n_b = ntot; }
-        }
-        const int32_t v = j < n_s ? org[opad((int)(j - n_b - d0))] : -2;
+        N.seek(j);
+        const int32_t v = j < N.s ? org[opad((int)(j - N.b - d0))] : -2;
         j++;
         fw[opad(m0 + (rev ? k1 - 1 - t : k0 + t))] = v;
     }
 }
 
 template <bool COHORT>
-__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_origin(const FetchOriginArgs A) {
+__global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_origin(const FetchArgs A) {
     __shared__ int32_t tile[WPB][FO_TILE];
     __shared__ int32_t fin[WPB][FO_TILE];
     __shared__ uint8_t stg[WPB][2 * TK_B];
@@ -1556,49 +1456,21 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_origin(const FetchOriginAr
     int32_t* org = tile[wave_in_block()];
     int32_t* fw = fin[wave_in_block()];
     uint8_t* st = stg[wave_in_block()];
-    const int64_t base = A.o_first + ((int64_t)blockIdx.x * WPB + wave_in_block()) * FT_W;
-    const int64_t fend = base + FT_W < A.F ? base + FT_W : A.F;
-    const int64_t w0 = base < 0 ? 0 : base;
-    int64_t f = w0;
-    if (f >= fend) return;
-    const int64_t g0 = base + (int64_t)lane * OPT;   // this lane's 16 bases
-    const int64_t* __restrict__ pre = A.pre;
-    DcCohortEntry E = A.E;   // the current span's sample
-    int cur = -1;
+    const FetchTile T = fetch_tile(A);
+    const int64_t base = T.base, w0 = T.w0, fend = T.fend;
+    if (w0 >= fend) return;
     MapCur mc{0, INT64_MAX, INT64_MAX, 0};   // (no bracket yet: the first piece searches)
     const int32_t* mc_of = nullptr;          // the map mc brackets (the readers of one shared reference have one)
-    int64_t i = wave_first(1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-    while (f < fend) {
-        if (pre[i + 1] <= f) {
-            i++;
-            if (pre[i + 1] <= f) i = wave_first(i + 1, A.nreg + 1, [&](int64_t m) { return pre[m] > f; }) - 1;
-        }
-        if (COHORT) {
-            const int sm = __builtin_amdgcn_readfirstlane(A.samp[i]);
-            if (sm != cur) {   // (wave-uniform: a scalar branch around scalar loads)
-                cur = sm;
-                E = cohort_entry(A.tab, sm);
-            }
-        }
-        const int64_t fe = pre[i + 1] < fend ? pre[i + 1] : fend;
-        const int64_t braw = A.beg[i];
-        const bool rev = A.all_rev || braw < 0;
-        const int64_t bg = braw & INT64_MAX;
-        const int64_t j0 = rev ? bg + (pre[i + 1] - fe) : bg + (f - pre[i]), j1 = j0 + (fe - f);   // j1 - j0 <= FT_W
+    fetch_spans<COHORT>(A, T, [&](const DcCohortEntry& E, int64_t j0, int64_t j1, bool rev, int64_t j, int k0, int k1) {
         if (E.S.rm.start != mc_of) {
             mc = MapCur{0, INT64_MAX, INT64_MAX, 0};
             mc_of = E.S.rm.start;
         }
         const FetchSpan sp = fetch_decode_span<true>(E.S, j0, j1, reinterpret_cast<uint8_t*>(org), st, &mc);
-        const int64_t ga = g0 > f ? g0 : f, gb = g0 + OPT < fe ? g0 + OPT : fe;
-        if (ga < gb) {
-            const int64_t j = rev ? j0 + (fe - gb) : j0 + (ga - f);
-            fetch_origin_walk(E.S, E.nn, E.ntot, org, fw, lane * OPT, j, sp.rn0, sp.d0, rev, (int)(ga - g0), (int)(gb - g0));
-        }
-        wave_sync();   // (the tile is read before the next span fills it)
-        f = fe;
-    }
-    wave_sync();   // fin[w0 - base, fend - base) is complete
+        if (k0 < k1) fetch_origin_walk(E, org, fw, lane * OPT, j, sp.rn0, sp.d0, rev, k0, k1);
+    });
+    // fin[w0 - base, fend - base) is complete
+    int32_t* out = reinterpret_cast<int32_t*>(A.out);
     for (int it = 0; it < 4 * (FT_W / 256); it++) {
         const int q = it * 64 + lane;
         const int64_t p0 = base + (int64_t)q * 4;   // the piece's first base
@@ -1606,7 +1478,7 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_origin(const FetchOriginAr
         int32_t w[4];
 #pragma unroll
         for (int t = 0; t < 4; t++) w[t] = fw[opad(q * 4 + t)];
-        int32_t* dst = A.out + p0;
+        int32_t* dst = out + p0;
         if (p0 >= w0 && p0 + 4 <= fend) {
             *reinterpret_cast<int4*>(dst) = make_int4(w[0], w[1], w[2], w[3]);
         } else {
@@ -1896,79 +1768,46 @@ int dc_format(const uint8_t* d_dec, int64_t nres, const DcRuns& nr, const DcRuns
     return 0;
 }
 
-int dc_fetch(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, bool upper,
-             uint8_t* d_out, hipStream_t s) {
-    if (F <= 0) return 0;
-    FetchArgs A{src, d_pre, d_beg, nreg, F, -(int64_t)((uintptr_t)d_out & 15), upper ? 0 : src.lr.n, d_out};
-    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
-    PROF_LAUNCH(PROF_FETCH, s, k_fetch, dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
-    SCCG_HIP(hipGetLastError());
-    return 0;
+namespace {
+// the kernel of a format (null: not a valid pair); COHORT: the source of each span from the table
+template <bool COHORT>
+void (*fetch_kernel(int enc, int dt))(FetchArgs) {
+    if (enc == FE_ASCII && dt == FD_U8) return k_fetch_enc<FE_ASCII, FD_U8, COHORT>;
+    if (enc == FE_INDEX && dt == FD_U8) return k_fetch_enc<FE_INDEX, FD_U8, COHORT>;
+    if (enc == FE_ONEHOT && dt == FD_U8) return k_fetch_enc<FE_ONEHOT, FD_U8, COHORT>;
+    if (enc == FE_ONEHOT && dt == FD_F16) return k_fetch_enc<FE_ONEHOT, FD_F16, COHORT>;
+    if (enc == FE_ONEHOT && dt == FD_BF16) return k_fetch_enc<FE_ONEHOT, FD_BF16, COHORT>;
+    if (enc == FE_ONEHOT && dt == FD_F32) return k_fetch_enc<FE_ONEHOT, FD_F32, COHORT>;
+    if (enc == FE_ORIGIN && dt == FD_I32) return k_fetch_origin<COHORT>;
+    return nullptr;
 }
+}  // namespace
 
-int dc_fetch_encoded(const DcFetchSrc& src, const int64_t* d_pre, const int64_t* d_beg, int64_t nreg, int64_t F, int enc, int dt,
-                     bool upper, bool all_rev, uint8_t* d_out, hipStream_t s) {
-    if (F <= 0) return 0;
-    const int es = dt == FD_U8 ? 1 : dt == FD_F32 ? 4 : 2, bpb = enc == FE_ONEHOT ? 4 * es : 1;
+int dc_fetch(const DcFetch& c, hipStream_t s) {
+    if (c.F <= 0) return 0;
+    void (*const kernel)(FetchArgs) = c.src ? fetch_kernel<false>(c.enc, c.dt) : fetch_kernel<true>(c.enc, c.dt);
+    if (!kernel) return SCCG_E_INVALID;
+    const uintptr_t at = (uintptr_t)c.d_out;
+    const uintptr_t es = c.dt == FD_U8 ? 1 : c.dt == FD_F16 || c.dt == FD_BF16 ? 2 : 4;   // element bytes
+    const uintptr_t bpb = c.enc == FE_ONEHOT ? 4 * es : c.enc == FE_ORIGIN ? es : 1;      // bytes per base
+    if (c.enc == FE_ORIGIN && at % bpb) return SCCG_E_INVALID;
     // whole bases per 16-byte piece need d_out on a base boundary; else every store is an element's
-    const bool elemwise = ((uintptr_t)d_out % (uintptr_t)bpb) != 0;
-    FetchEncArgs A{src, d_pre, d_beg, nreg, F, elemwise ? 0 : -(int64_t)(((uintptr_t)d_out & 15) / (uintptr_t)bpb),
-                   upper ? 0 : src.lr.n, all_rev ? 1u : 0u, elemwise ? 1u : 0u, d_out};
-    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
-#define SCCG_FETCH_ENC(E, D) \
-    PROF_LAUNCH(PROF_FETCH, s, (k_fetch_enc<E, D>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A)
-    if (enc == FE_ASCII && dt == FD_U8) SCCG_FETCH_ENC(FE_ASCII, FD_U8);
-    else if (enc == FE_INDEX && dt == FD_U8) SCCG_FETCH_ENC(FE_INDEX, FD_U8);
-    else if (enc == FE_ONEHOT && dt == FD_U8) SCCG_FETCH_ENC(FE_ONEHOT, FD_U8);
-    else if (enc == FE_ONEHOT && dt == FD_F16) SCCG_FETCH_ENC(FE_ONEHOT, FD_F16);
-    else if (enc == FE_ONEHOT && dt == FD_BF16) SCCG_FETCH_ENC(FE_ONEHOT, FD_BF16);
-    else if (enc == FE_ONEHOT && dt == FD_F32) SCCG_FETCH_ENC(FE_ONEHOT, FD_F32);
-    else return SCCG_E_INVALID;
-#undef SCCG_FETCH_ENC
-    SCCG_HIP(hipGetLastError());
-    return 0;
-}
-
-int dc_fetch_cohort(const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg, const int32_t* d_samp, int64_t nreg,
-                    int64_t F, int enc, int dt, bool upper, bool all_rev, uint8_t* d_out, hipStream_t s) {
-    if (F <= 0) return 0;
-    const int es = dt == FD_U8 ? 1 : dt == FD_F32 ? 4 : 2, bpb = enc == FE_ONEHOT ? 4 * es : 1;
-    const bool elemwise = ((uintptr_t)d_out % (uintptr_t)bpb) != 0;   // (as dc_fetch_encoded)
-    FetchCohortArgs A{d_tab, d_pre, d_beg, d_samp, nreg, F, elemwise ? 0 : -(int64_t)(((uintptr_t)d_out & 15) / (uintptr_t)bpb),
-                      all_rev ? 1u : 0u, elemwise ? 1u : 0u, upper ? 1u : 0u, d_out};
-    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
-#define SCCG_FETCH_COHORT(E, D) \
-    PROF_LAUNCH(PROF_FETCH, s, (k_fetch_cohort<E, D>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A)
-    if (enc == FE_ASCII && dt == FD_U8) SCCG_FETCH_COHORT(FE_ASCII, FD_U8);
-    else if (enc == FE_INDEX && dt == FD_U8) SCCG_FETCH_COHORT(FE_INDEX, FD_U8);
-    else if (enc == FE_ONEHOT && dt == FD_U8) SCCG_FETCH_COHORT(FE_ONEHOT, FD_U8);
-    else if (enc == FE_ONEHOT && dt == FD_F16) SCCG_FETCH_COHORT(FE_ONEHOT, FD_F16);
-    else if (enc == FE_ONEHOT && dt == FD_BF16) SCCG_FETCH_COHORT(FE_ONEHOT, FD_BF16);
-    else if (enc == FE_ONEHOT && dt == FD_F32) SCCG_FETCH_COHORT(FE_ONEHOT, FD_F32);
-    else return SCCG_E_INVALID;
-#undef SCCG_FETCH_COHORT
-    SCCG_HIP(hipGetLastError());
-    return 0;
-}
-
-int dc_fetch_origin(const DcFetchSrc* src, const DcCohortEntry* d_tab, const int64_t* d_pre, const int64_t* d_beg,
-                    const int32_t* d_samp, int64_t nreg, int64_t F, bool all_rev, int32_t* d_out, hipStream_t s) {
-    if (F <= 0) return 0;
-    if ((uintptr_t)d_out & 3) return SCCG_E_INVALID;
-    FetchOriginArgs A{};
-    if (src) A.E = DcCohortEntry{*src, src->nr.n, src->lr.n, src->nr.total};
-    A.tab = d_tab;
-    A.pre = d_pre;
-    A.beg = d_beg;
-    A.samp = d_samp;
-    A.nreg = nreg;
-    A.F = F;
-    A.o_first = -(int64_t)(((uintptr_t)d_out & 15) / 4);   // whole 16-byte pieces of 4 bases
-    A.all_rev = all_rev ? 1u : 0u;
-    A.out = d_out;
-    const int64_t nblk = (F - A.o_first + OB - 1) / OB;
-    if (src) PROF_LAUNCH(PROF_FETCH, s, (k_fetch_origin<false>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
-    else PROF_LAUNCH(PROF_FETCH, s, (k_fetch_origin<true>), dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
+    const bool elemwise = at % bpb != 0;
+    FetchArgs A{};
+    if (c.src) A.E = DcCohortEntry{*c.src, c.src->nr.n, c.src->lr.n, c.src->nr.total};
+    A.tab = c.d_tab;
+    A.pre = c.d_pre;
+    A.beg = c.d_beg;
+    A.samp = c.d_samp;
+    A.nreg = c.nreg;
+    A.F = c.F;
+    A.o_first = elemwise ? 0 : -(int64_t)((at & 15) / bpb);
+    A.all_rev = c.all_rev ? 1u : 0u;
+    A.elemwise = elemwise ? 1u : 0u;
+    A.upper = c.upper ? 1u : 0u;
+    A.out = c.d_out;
+    const int64_t nblk = (c.F - A.o_first + OB - 1) / OB;
+    PROF_LAUNCH(PROF_FETCH, s, kernel, dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
     SCCG_HIP(hipGetLastError());
     return 0;
 }

@@ -235,6 +235,46 @@ struct sccg_reference {
     }
 };
 
+// A fetch's staging, held by a reader and by a cohort, grown on demand: the region image (device
+// copy and its pinned host image) and the host calls' device output.  The reserves answer the
+// error of an allocation that failed, its size in *cap.
+struct FetchStage {
+    void* d_reg = nullptr;
+    int64_t* h_reg = nullptr;
+    size_t reg_cap = 0;
+    void* d_out = nullptr;
+    size_t out_cap = 0;
+    hipError_t reserve_regions(size_t bytes, size_t* cap) {
+        if (reg_cap >= bytes) return hipSuccess;
+        *cap = bytes + bytes / 2 + 4096;
+        if (d_reg) (void)hipFree(d_reg);
+        if (h_reg) (void)hipHostFree(h_reg);
+        d_reg = nullptr;
+        h_reg = nullptr;
+        reg_cap = 0;
+        hipError_t e = hipMalloc(&d_reg, *cap);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h_reg), *cap, hipHostMallocDefault);
+        if (e == hipSuccess) reg_cap = *cap;
+        return e;
+    }
+    hipError_t reserve_out(size_t bytes, size_t* cap) {
+        if (out_cap >= bytes + 16) return hipSuccess;
+        *cap = bytes + bytes / 4 + 4096;
+        if (d_out) (void)hipFree(d_out);
+        d_out = nullptr;
+        out_cap = 0;
+        const hipError_t e = hipMalloc(&d_out, *cap);
+        if (e == hipSuccess) out_cap = *cap;
+        else d_out = nullptr;
+        return e;
+    }
+    void free() {
+        if (d_reg) (void)hipFree(d_reg);
+        if (h_reg) (void)hipHostFree(h_reg);
+        if (d_out) (void)hipFree(d_out);
+    }
+};
+
 // A region reader (sccg_reader_open): what a fetch reads, in device memory of its own -- never a
 // pooled slot of the context, which the next compress / reconstruct reuses.
 struct sccg_reader {
@@ -246,11 +286,7 @@ struct sccg_reader {
     int64_t length = 0;         // bases in the sequence (reconstruct_impl's nres)
     bool has_coords = false;    // src.rm turns R' positions into the reference's (the origin fetch)
     std::string header;         // the header line, '>' included, no '\n'; empty: none
-    void* d_reg = nullptr;      // a fetch's region list: device copy and its pinned host image
-    int64_t* h_reg = nullptr;
-    size_t reg_cap = 0;
-    void* d_out = nullptr;      // sccg_reader_fetch's device output
-    size_t out_cap = 0;
+    FetchStage stage;
 };
 
 // A cohort (sccg_cohort_create): the device table of its readers' sources, and region staging and a
@@ -260,11 +296,7 @@ struct sccg_cohort {
     std::vector<int64_t> length;   // per sample
     std::vector<uint8_t> coords;   // per sample: its reader has reference coordinates
     void* d_tab = nullptr;         // DcCohortEntry per sample
-    void* d_reg = nullptr;         // a fetch's region list: device copy and its pinned host image
-    int64_t* h_reg = nullptr;
-    size_t reg_cap = 0;
-    void* d_out = nullptr;         // sccg_cohort_fetch's device output
-    size_t out_cap = 0;
+    FetchStage stage;
 };
 
 #define TRY(expr)                                  \
@@ -1521,9 +1553,7 @@ void reader_free(sccg_reader* rd) {
     if (!rd) return;
     (void)hipSetDevice(rd->ctx->device);
     if (rd->mem) (void)hipFree(rd->mem);
-    if (rd->d_reg) (void)hipFree(rd->d_reg);
-    if (rd->h_reg) (void)hipHostFree(rd->h_reg);
-    if (rd->d_out) (void)hipFree(rd->d_out);
+    rd->stage.free();
     if (rd->ref) reference_drop(rd->ref);
     delete rd;
 }
@@ -1567,9 +1597,15 @@ size_t fetch_format_bpb(const sccg_fetch_format* f) {
     return f->dtype == SCCG_DT_U8 ? 4 : f->dtype == SCCG_DT_F16 || f->dtype == SCCG_DT_BF16 ? 8 : f->dtype == SCCG_DT_F32 ? 16 : 0;
 }
 
-// the element d_out must be aligned to
-size_t fetch_format_elem(const sccg_fetch_format* f, size_t bpb) {
-    return f->encoding == SCCG_ENC_ONEHOT ? bpb / 4 : f->encoding == SCCG_ENC_ORIGIN ? 4 : 1;
+// the format's check, the first of every encoded entry point: *bpb = its bytes per base; d_out (the
+// device calls'; NULL passes) must be aligned to its element
+int fetch_format_check(sccg_ctx* ctx, const sccg_fetch_format* f, const void* d_out, size_t* bpb) {
+    *bpb = fetch_format_bpb(f);
+    if (!*bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
+                                f->encoding, f->dtype, f->flags, f->reserved);
+    const size_t es = f->encoding == SCCG_ENC_ONEHOT ? *bpb / 4 : f->encoding == SCCG_ENC_ORIGIN ? 4 : 1;
+    if ((uintptr_t)d_out % es) return ctx->fail(SCCG_E_INVALID, "d_out is not aligned to the %zu-byte element", es);
+    return SCCG_OK;
 }
 
 // an ORIGIN fetch needs a reader with reference coordinates (checked after the format, for ORIGIN only)
@@ -1581,45 +1617,111 @@ int fetch_coords_check(sccg_reader* rd, const sccg_fetch_format* fmt) {
                                    "(open it through a sccg_reference with SCCG_REF_COORDS)");
 }
 
-// regions validated, F > 0, d_out holds the output: the region list in one copy, one launch, one
-// sync.  fmt NULL: sccg_reader_fetch's bytes (k_fetch); else the encoded form, strand (may be NULL)
-// travelling as bit 63 of the begins
-int fetch_run(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t F, uint32_t flags, uint8_t* d_out,
-              hipStream_t s, const sccg_fetch_format* fmt = nullptr, const uint8_t* strand = nullptr) {
-    sccg_ctx* ctx = rd->ctx;
-    const size_t words = 2 * n + 1, bytes = words * sizeof(int64_t);
-    if (rd->reg_cap < bytes) {
-        const size_t cap = bytes + bytes / 2 + 4096;
-        if (rd->d_reg) (void)hipFree(rd->d_reg);
-        if (rd->h_reg) (void)hipHostFree(rd->h_reg);
-        rd->d_reg = nullptr;
-        rd->h_reg = nullptr;
-        rd->reg_cap = 0;
-        hipError_t e = hipMalloc(&rd->d_reg, cap);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&rd->h_reg), cap, hipHostMallocDefault);
-        if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
-        rd->reg_cap = cap;
-    }
-    // [0, n]: exclusive prefix of the lengths (the flat output space -> region), (n, 2n]: begins
-    int64_t* h = rd->h_reg;
+// A region as the region image takes it, and the two lists it is read from: a reader's regions with
+// their strand bytes (may be NULL), and a cohort's.
+struct FetchItem {
+    int64_t begin, end;
+    bool rev;
+    int32_t sample;
+};
+struct ReaderRegions {
+    static constexpr bool samples = false;
+    const sccg_region* r;
+    const uint8_t* strand;
+    FetchItem operator()(size_t i) const { return FetchItem{r[i].begin, r[i].end, strand && strand[i], 0}; }
+};
+struct CohortRegions {
+    static constexpr bool samples = true;
+    const sccg_cohort_region* r;
+    FetchItem operator()(size_t i) const { return FetchItem{r[i].begin, r[i].end, (r[i].flags & 1u) != 0, r[i].sample}; }
+};
+
+// the launcher's call for a source (src, or a cohort's table) and a format (NULL: sccg_reader_fetch's
+// plain bytes, `flags` its flags); the region image and d_out are fetch_run's to fill in
+DcFetch fetch_call(const DcFetchSrc* src, const void* d_tab, const sccg_fetch_format* fmt, uint32_t flags) {
+    DcFetch c{};
+    c.src = src;
+    c.d_tab = reinterpret_cast<const DcCohortEntry*>(d_tab);
+    c.enc = fmt ? (int)fmt->encoding : (int)SCCG_ENC_ASCII;
+    c.dt = fmt ? (int)fmt->dtype : (int)SCCG_DT_U8;
+    c.upper = (flags & SCCG_FETCH_UPPER) != 0;
+    c.all_rev = fmt && (flags & SCCG_FETCH_REVCOMP) != 0;
+    return c;
+}
+
+// Regions validated, at least one base, d_out holds the output.  ONE pinned image -- [0, n] the
+// exclusive prefix of the lengths (the flat output space -> region), (n, 2n] the begins with the
+// strand in bit 63, then, for a cohort, the samples as int32 -- in one copy; one launch; one sync.
+template <typename Regions>
+int fetch_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, DcFetch c, void* d_out, hipStream_t s) {
+    constexpr bool samples = Regions::samples;   // (known to the packing loop: 100,000 regions are packed inside the call)
+    const size_t words = 2 * n + 1, bytes = words * sizeof(int64_t) + (samples ? n * sizeof(int32_t) : 0);
+    size_t cap = 0;
+    const hipError_t e = st.reserve_regions(bytes, &cap);
+    if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
+    int64_t* h = st.h_reg;
+    int32_t* hs = reinterpret_cast<int32_t*>(h + words);
     int64_t at = 0;
     for (size_t i = 0; i < n; i++) {
+        const FetchItem r = regions(i);
         h[i] = at;
-        h[n + 1 + i] = regions[i].begin | (strand && strand[i] ? INT64_MIN : 0);
-        at += regions[i].end - regions[i].begin;
+        h[n + 1 + i] = r.begin | (r.rev ? INT64_MIN : 0);
+        if (samples) hs[i] = r.sample;
+        at += r.end - r.begin;
     }
     h[n] = at;
-    int64_t* d = reinterpret_cast<int64_t*>(rd->d_reg);
+    int64_t* d = reinterpret_cast<int64_t*>(st.d_reg);
     HIPTRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    if (fmt && fmt->encoding == SCCG_ENC_ORIGIN)
-        TRY(dc_fetch_origin(&rd->src, nullptr, d, d + n + 1, nullptr, (int64_t)n, F, (flags & SCCG_FETCH_REVCOMP) != 0,
-                            reinterpret_cast<int32_t*>(d_out), s));
-    else if (fmt)
-        TRY(dc_fetch_encoded(rd->src, d, d + n + 1, (int64_t)n, F, (int)fmt->encoding, (int)fmt->dtype,
-                             (flags & SCCG_FETCH_UPPER) != 0, (flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
-    else
-        TRY(dc_fetch(rd->src, d, d + n + 1, (int64_t)n, F, (flags & SCCG_FETCH_UPPER) != 0, d_out, s));
+    c.d_pre = d;
+    c.d_beg = d + n + 1;
+    c.d_samp = samples ? reinterpret_cast<const int32_t*>(d + words) : nullptr;
+    c.nreg = (int64_t)n;
+    c.F = at;
+    c.d_out = d_out;
+    TRY(dc_fetch(c, s));
     HIPTRY(hipStreamSynchronize(s));
+    return SCCG_OK;
+}
+
+// The device calls' tail, the regions checked: the size, the capacity, the run on the caller's stream.
+template <typename Regions>
+int fetch_to_device(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, const DcFetch& c, size_t bytes, void* d_out,
+                    size_t out_cap, size_t* out_len, void* stream) {
+    *out_len = bytes;
+    if (!d_out) return SCCG_OK;   // size query
+    if (bytes > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu bytes", bytes);
+    if (bytes == 0) return SCCG_OK;
+    HIPTRY(hipSetDevice(ctx->device));
+    return fetch_run(ctx, st, regions, n, c, d_out, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+// The host calls' tail, the regions checked: the run into the stage's own device output, grown on
+// demand, and the copy into a malloc'd, NUL-terminated buffer.  On failure the buffer is freed and
+// *out is the caller's as it was.
+template <typename Regions>
+int fetch_to_host(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, const DcFetch& c, size_t bytes, sccg_buf* out) {
+    char* h = (char*)malloc(bytes + 1);
+    if (!h) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
+    const auto fill = [&]() -> int {
+        if (bytes == 0) return SCCG_OK;
+        HIPTRY(hipSetDevice(ctx->device));
+        size_t cap = 0;
+        hipError_t e = st.reserve_out(bytes, &cap);
+        if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
+        const int rc = fetch_run(ctx, st, regions, n, c, st.d_out, ctx->stream);
+        if (rc) return rc;
+        e = hipMemcpy(h, st.d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__));
+        return SCCG_OK;
+    };
+    const int rc = fill();
+    if (rc) {
+        free(h);
+        return rc;
+    }
+    h[bytes] = 0;
+    out->data = h;
+    out->len = bytes;
     return SCCG_OK;
 }
 
@@ -1721,21 +1823,17 @@ void cohort_free(sccg_cohort* co) {
     if (!co) return;
     (void)hipSetDevice(co->ctx->device);
     if (co->d_tab) (void)hipFree(co->d_tab);
-    if (co->d_reg) (void)hipFree(co->d_reg);
-    if (co->h_reg) (void)hipHostFree(co->h_reg);
-    if (co->d_out) (void)hipFree(co->d_out);
+    co->stage.free();
     delete co;
 }
 
-// the format (as the encoded fetch's), then every region: its flags, its sample, its range in that
-// sample; SCCG_E_INVALID names the first offender.  *F: the regions' total length
-int cohort_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt, size_t* bpb, int64_t* F) {
+// after the format's check, every region: its flags, its sample, its range in that sample;
+// SCCG_E_INVALID names the first offender.  *F: the regions' total length
+int cohort_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt, int64_t* F) {
     sccg_ctx* ctx = co->ctx;
-    *bpb = fetch_format_bpb(fmt);
-    if (!*bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
-                                fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
     if (!regions && n) return ctx->fail(SCCG_E_INVALID, "null region list");
     const int64_t ns = (int64_t)co->length.size();
+    const bool origin = fmt->encoding == SCCG_ENC_ORIGIN;   // (read once: 100,000 regions pass this loop inside the call)
     int64_t tot = 0;
     for (size_t i = 0; i < n; i++) {
         const sccg_cohort_region& r = regions[i];
@@ -1746,54 +1844,12 @@ int cohort_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, c
         if (r.begin < 0 || r.end < r.begin || r.end > len)
             return ctx->fail(SCCG_E_INVALID, "region %zu [%lld, %lld) is outside sample %d's sequence [0, %lld)", i,
                              (long long)r.begin, (long long)r.end, (int)r.sample, (long long)len);
-        if (fmt->encoding == SCCG_ENC_ORIGIN && !co->coords[(size_t)r.sample])
+        if (origin && !co->coords[(size_t)r.sample])
             return ctx->fail(SCCG_E_UNSUPPORTED, "region %zu reads sample %d, whose reader has no reference coordinates "
                              "(open it through a sccg_reference with SCCG_REF_COORDS)", i, (int)r.sample);
         tot += r.end - r.begin;
     }
     *F = tot;
-    return SCCG_OK;
-}
-
-// fetch_run for a cohort: one pinned image -- [0, n] the prefix of the lengths, (n, 2n] the begins
-// with the strand in bit 63, then the samples as int32 -- in one copy; one launch; one sync
-int cohort_run(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, int64_t F, const sccg_fetch_format* fmt,
-               uint8_t* d_out, hipStream_t s) {
-    sccg_ctx* ctx = co->ctx;
-    const size_t words = 2 * n + 1, bytes = words * sizeof(int64_t) + n * sizeof(int32_t);
-    if (co->reg_cap < bytes) {
-        const size_t cap = bytes + bytes / 2 + 4096;
-        if (co->d_reg) (void)hipFree(co->d_reg);
-        if (co->h_reg) (void)hipHostFree(co->h_reg);
-        co->d_reg = nullptr;
-        co->h_reg = nullptr;
-        co->reg_cap = 0;
-        hipError_t e = hipMalloc(&co->d_reg, cap);
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&co->h_reg), cap, hipHostMallocDefault);
-        if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
-        co->reg_cap = cap;
-    }
-    int64_t* h = co->h_reg;
-    int32_t* hs = reinterpret_cast<int32_t*>(h + words);
-    int64_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        h[i] = at;
-        h[n + 1 + i] = regions[i].begin | ((regions[i].flags & 1u) ? INT64_MIN : 0);
-        hs[i] = regions[i].sample;
-        at += regions[i].end - regions[i].begin;
-    }
-    h[n] = at;
-    int64_t* d = reinterpret_cast<int64_t*>(co->d_reg);
-    HIPTRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-    if (fmt->encoding == SCCG_ENC_ORIGIN)
-        TRY(dc_fetch_origin(nullptr, reinterpret_cast<const DcCohortEntry*>(co->d_tab), d, d + n + 1,
-                            reinterpret_cast<const int32_t*>(d + words), (int64_t)n, F, (fmt->flags & SCCG_FETCH_REVCOMP) != 0,
-                            reinterpret_cast<int32_t*>(d_out), s));
-    else
-        TRY(dc_fetch_cohort(reinterpret_cast<const DcCohortEntry*>(co->d_tab), d, d + n + 1,
-                            reinterpret_cast<const int32_t*>(d + words), (int64_t)n, F, (int)fmt->encoding, (int)fmt->dtype,
-                            (fmt->flags & SCCG_FETCH_UPPER) != 0, (fmt->flags & SCCG_FETCH_REVCOMP) != 0, d_out, s));
-    HIPTRY(hipStreamSynchronize(s));
     return SCCG_OK;
 }
 
@@ -1953,46 +2009,20 @@ const char* sccg_reader_header(const sccg_reader* reader, size_t* len) {
 int sccg_reader_fetch_device(sccg_reader* reader, const sccg_region* regions, size_t n, uint32_t flags, void* d_out,
                              size_t out_cap, size_t* out_len, void* stream) {
     if (!reader || !out_len) return SCCG_E_INVALID;
-    sccg_ctx* ctx = reader->ctx;
     int64_t F = 0;
     const int rc = fetch_check(reader, regions, n, &F);
     if (rc) return rc;
-    *out_len = (size_t)F;
-    if (!d_out) return SCCG_OK;   // size query
-    if ((size_t)F > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %lld bytes", (long long)F);
-    if (F == 0) return SCCG_OK;
-    HIPTRY(hipSetDevice(ctx->device));
-    return fetch_run(reader, regions, n, F, flags, (uint8_t*)d_out, stream ? (hipStream_t)stream : ctx->stream);
+    return fetch_to_device(reader->ctx, reader->stage, ReaderRegions{regions, nullptr}, n,
+                           fetch_call(&reader->src, nullptr, nullptr, flags), (size_t)F, d_out, out_cap, out_len, stream);
 }
 
 int sccg_reader_fetch(sccg_reader* reader, const sccg_region* regions, size_t n, uint32_t flags, sccg_buf* out) {
     if (!reader || !out) return SCCG_E_INVALID;
-    sccg_ctx* ctx = reader->ctx;
     int64_t F = 0;
-    int rc = fetch_check(reader, regions, n, &F);
+    const int rc = fetch_check(reader, regions, n, &F);
     if (rc) return rc;   // (nothing written: *out is the caller's as it was)
-    char* h = (char*)malloc((size_t)F + 1);
-    if (!h) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
-    if (F > 0) {
-        HIPTRY(hipSetDevice(ctx->device));
-        if (reader->out_cap < (size_t)F + 16) {   // the reader's own output buffer, grown on demand
-            if (reader->d_out) (void)hipFree(reader->d_out);
-            reader->d_out = nullptr;
-            reader->out_cap = 0;
-            const size_t cap = (size_t)F + (size_t)F / 4 + 4096;
-            const hipError_t e = hipMalloc(&reader->d_out, cap);
-            if (e != hipSuccess) { free(h); reader->d_out = nullptr; return reader_alloc_fail(ctx, e, cap); }
-            reader->out_cap = cap;
-        }
-        rc = fetch_run(reader, regions, n, F, flags, (uint8_t*)reader->d_out, ctx->stream);
-        if (rc) { free(h); return rc; }
-        const hipError_t e = hipMemcpy(h, reader->d_out, (size_t)F, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(h); return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__)); }
-    }
-    h[F] = 0;
-    out->data = h;
-    out->len = (size_t)F;
-    return SCCG_OK;
+    return fetch_to_host(reader->ctx, reader->stage, ReaderRegions{regions, nullptr}, n,
+                         fetch_call(&reader->src, nullptr, nullptr, flags), (size_t)F, out);
 }
 
 size_t sccg_fetch_bytes_per_base(const sccg_fetch_format* fmt) { return fetch_format_bpb(fmt); }
@@ -2000,58 +2030,27 @@ size_t sccg_fetch_bytes_per_base(const sccg_fetch_format* fmt) { return fetch_fo
 int sccg_reader_fetch_encoded_device(sccg_reader* reader, const sccg_region* regions, size_t n, const uint8_t* strand,
                                      const sccg_fetch_format* fmt, void* d_out, size_t out_cap, size_t* out_len, void* stream) {
     if (!reader || !fmt || !out_len) return SCCG_E_INVALID;
-    sccg_ctx* ctx = reader->ctx;
-    const size_t bpb = fetch_format_bpb(fmt);
-    if (!bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
-                               fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
-    const size_t es = fetch_format_elem(fmt, bpb);
-    if ((uintptr_t)d_out % es) return ctx->fail(SCCG_E_INVALID, "d_out is not aligned to the %zu-byte element", es);
+    size_t bpb = 0;
     int64_t F = 0;
-    int rc = fetch_coords_check(reader, fmt);
+    int rc = fetch_format_check(reader->ctx, fmt, d_out, &bpb);
+    if (!rc) rc = fetch_coords_check(reader, fmt);
     if (!rc) rc = fetch_check(reader, regions, n, &F);
     if (rc) return rc;
-    *out_len = (size_t)F * bpb;
-    if (!d_out) return SCCG_OK;   // size query
-    if ((size_t)F * bpb > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu bytes", (size_t)F * bpb);
-    if (F == 0) return SCCG_OK;
-    HIPTRY(hipSetDevice(ctx->device));
-    return fetch_run(reader, regions, n, F, fmt->flags, (uint8_t*)d_out, stream ? (hipStream_t)stream : ctx->stream, fmt, strand);
+    return fetch_to_device(reader->ctx, reader->stage, ReaderRegions{regions, strand}, n,
+                           fetch_call(&reader->src, nullptr, fmt, fmt->flags), (size_t)F * bpb, d_out, out_cap, out_len, stream);
 }
 
 int sccg_reader_fetch_encoded(sccg_reader* reader, const sccg_region* regions, size_t n, const uint8_t* strand,
                               const sccg_fetch_format* fmt, sccg_buf* out) {
     if (!reader || !fmt || !out) return SCCG_E_INVALID;
-    sccg_ctx* ctx = reader->ctx;
-    const size_t bpb = fetch_format_bpb(fmt);
-    if (!bpb) return ctx->fail(SCCG_E_INVALID, "invalid fetch format (encoding %u, dtype %u, flags %u, reserved %u)",
-                               fmt->encoding, fmt->dtype, fmt->flags, fmt->reserved);
+    size_t bpb = 0;
     int64_t F = 0;
-    int rc = fetch_coords_check(reader, fmt);
+    int rc = fetch_format_check(reader->ctx, fmt, nullptr, &bpb);
+    if (!rc) rc = fetch_coords_check(reader, fmt);
     if (!rc) rc = fetch_check(reader, regions, n, &F);
     if (rc) return rc;   // (nothing written: *out is the caller's as it was)
-    const size_t bytes = (size_t)F * bpb;
-    char* h = (char*)malloc(bytes + 1);
-    if (!h) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
-    if (F > 0) {
-        HIPTRY(hipSetDevice(ctx->device));
-        if (reader->out_cap < bytes + 16) {   // the reader's own output buffer, grown on demand
-            if (reader->d_out) (void)hipFree(reader->d_out);
-            reader->d_out = nullptr;
-            reader->out_cap = 0;
-            const size_t cap = bytes + bytes / 4 + 4096;
-            const hipError_t e = hipMalloc(&reader->d_out, cap);
-            if (e != hipSuccess) { free(h); reader->d_out = nullptr; return reader_alloc_fail(ctx, e, cap); }
-            reader->out_cap = cap;
-        }
-        rc = fetch_run(reader, regions, n, F, fmt->flags, (uint8_t*)reader->d_out, ctx->stream, fmt, strand);
-        if (rc) { free(h); return rc; }
-        const hipError_t e = hipMemcpy(h, reader->d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(h); return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__)); }
-    }
-    h[bytes] = 0;
-    out->data = h;
-    out->len = bytes;
-    return SCCG_OK;
+    return fetch_to_host(reader->ctx, reader->stage, ReaderRegions{regions, strand}, n,
+                         fetch_call(&reader->src, nullptr, fmt, fmt->flags), (size_t)F * bpb, out);
 }
 
 int sccg_reference_open_device(sccg_ctx* ctx, const void* d_ref_fa, size_t ref_len, uint32_t forms, sccg_reference** out,
@@ -2154,54 +2153,24 @@ size_t sccg_cohort_samples(const sccg_cohort* cohort) { return cohort ? cohort->
 int sccg_cohort_fetch_device(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt,
                              void* d_out, size_t out_cap, size_t* out_len, void* stream) {
     if (!cohort || !fmt || !out_len) return SCCG_E_INVALID;
-    sccg_ctx* ctx = cohort->ctx;
     size_t bpb = 0;
     int64_t F = 0;
-    const size_t bpb0 = fetch_format_bpb(fmt);
-    if (bpb0) {
-        const size_t es = fetch_format_elem(fmt, bpb0);
-        if ((uintptr_t)d_out % es) return ctx->fail(SCCG_E_INVALID, "d_out is not aligned to the %zu-byte element", es);
-    }
-    const int rc = cohort_check(cohort, regions, n, fmt, &bpb, &F);
+    int rc = fetch_format_check(cohort->ctx, fmt, d_out, &bpb);
+    if (!rc) rc = cohort_check(cohort, regions, n, fmt, &F);
     if (rc) return rc;
-    *out_len = (size_t)F * bpb;
-    if (!d_out) return SCCG_OK;   // size query
-    if ((size_t)F * bpb > out_cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu bytes", (size_t)F * bpb);
-    if (F == 0) return SCCG_OK;
-    HIPTRY(hipSetDevice(ctx->device));
-    return cohort_run(cohort, regions, n, F, fmt, (uint8_t*)d_out, stream ? (hipStream_t)stream : ctx->stream);
+    return fetch_to_device(cohort->ctx, cohort->stage, CohortRegions{regions}, n, fetch_call(nullptr, cohort->d_tab, fmt, fmt->flags),
+                           (size_t)F * bpb, d_out, out_cap, out_len, stream);
 }
 
 int sccg_cohort_fetch(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, const sccg_fetch_format* fmt, sccg_buf* out) {
     if (!cohort || !fmt || !out) return SCCG_E_INVALID;
-    sccg_ctx* ctx = cohort->ctx;
     size_t bpb = 0;
     int64_t F = 0;
-    int rc = cohort_check(cohort, regions, n, fmt, &bpb, &F);
+    int rc = fetch_format_check(cohort->ctx, fmt, nullptr, &bpb);
+    if (!rc) rc = cohort_check(cohort, regions, n, fmt, &F);
     if (rc) return rc;   // (nothing written: *out is the caller's as it was)
-    const size_t bytes = (size_t)F * bpb;
-    char* h = (char*)malloc(bytes + 1);
-    if (!h) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
-    if (F > 0) {
-        HIPTRY(hipSetDevice(ctx->device));
-        if (cohort->out_cap < bytes + 16) {   // the cohort's own output buffer, grown on demand
-            if (cohort->d_out) (void)hipFree(cohort->d_out);
-            cohort->d_out = nullptr;
-            cohort->out_cap = 0;
-            const size_t cap = bytes + bytes / 4 + 4096;
-            const hipError_t e = hipMalloc(&cohort->d_out, cap);
-            if (e != hipSuccess) { free(h); cohort->d_out = nullptr; return reader_alloc_fail(ctx, e, cap); }
-            cohort->out_cap = cap;
-        }
-        rc = cohort_run(cohort, regions, n, F, fmt, (uint8_t*)cohort->d_out, ctx->stream);
-        if (rc) { free(h); return rc; }
-        const hipError_t e = hipMemcpy(h, cohort->d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(h); return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__)); }
-    }
-    h[bytes] = 0;
-    out->data = h;
-    out->len = bytes;
-    return SCCG_OK;
+    return fetch_to_host(cohort->ctx, cohort->stage, CohortRegions{regions}, n, fetch_call(nullptr, cohort->d_tab, fmt, fmt->flags),
+                         (size_t)F * bpb, out);
 }
 
 // match_sequences seam (compression.cpp:36): local segments or the windowed global walk

@@ -273,6 +273,35 @@ def test_cohort_parity(case, enc, dt):
         chk(rnd[:60], "upper", upper=True)
 
 
+# the smallest lengths that cross a 16-byte piece, a wave's 1,024 bases and a block's 4,096 (the
+# encoded reader tests' list)
+LENGTHS = [15, 50000, 17, 4097, 4096, 63, 4095, 1, 65, 16, 64]
+
+
+def test_cohort_of_one_reader_is_that_reader(ctx, case):
+    """The two arms of the fetch kernels' shared template against each other: a cohort made of one
+    reader alone answers (0, b, e, rev) with the bytes of that reader's fetch_encoded, for every
+    format and for origin -- regions of LENGTHS around one position (they change region inside a
+    lane), forward, reversed and alternating, with a run of empty regions in the middle."""
+    hand_rfa, hand_rec = HAND["lowercase_spanning_n"]
+    n_run = next(k for k, c in enumerate(case.truths[2]) if k > 20_000 and c in b"N")   # inside the generated target
+    for rfa, rec, c, truth in ((case.rfa, case.recs[2], n_run, case.truths[2]),
+                               (hand_rfa, hand_rec, 12, cohortlib.hand_sequence(hand_rfa, hand_rec))):
+        with ctx.open_reference(rfa, coords=True) as ref, ref.open_reader(rec) as rd, sccg.Cohort([rd]) as co:
+            L = rd.length
+            assert L == len(truth) and rd.has_coords
+            regions = fetchlib.clamp([(c - n // 3, c - n // 3 + n) for n in LENGTHS], L)
+            regions[6:6] = [(c, c)] * 70
+            assert sum(e - b for b, e in regions) > min(L, 50_000)
+            for strands in ([0] * len(regions), [1] * len(regions), [k & 1 for k in range(len(regions))]):
+                items = [(0, b, e, r) for (b, e), r in zip(regions, strands)]
+                for enc, dt in ALL_FORMATS + [("origin", "i32")]:
+                    want = rd.fetch_encoded(regions, enc, dt, strand=strands)
+                    assert co.fetch_encoded(items, enc, dt) == want, (len(rec), strands[:2], enc, dt)
+                    if enc == "ascii":
+                        assert want == b"".join(fetchlib.strand_bytes(truth, regions, strands)), (len(rec), strands[:2])
+
+
 @pytest.mark.parametrize("s", range(5), ids=cohortlib.KINDS)
 def test_cohort_boundaries_per_sample(case, s):
     """N, case and token boundaries of sample s as region begins and ends, other samples between."""
