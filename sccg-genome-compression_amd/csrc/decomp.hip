@@ -1283,11 +1283,13 @@ constexpr int FD_U8 = 0, FD_F16 = 1, FD_BF16 = 2, FD_F32 = 3, FD_I32 = 4;   // S
 
 // IUPAC complement of an uppercase letter as its index 0..25, 13 letters x 5 bits per word
 // (A<->T C<->G R<->Y K<->M B<->V D<->H; every other letter is its own)
+// Thirteen 5-bit entries fill 65 bits: 'Z' (the last of the second word, and its own complement)
+// has no entry -- its value would lose bit 64 -- and comp_ascii leaves it alone with the non-letters.
 constexpr uint64_t comp_word(int half) {
     const char* from = "ACGTRYKMBVDH";
     const char* to = "TGCAYRMKVBHD";
     uint64_t w = 0;
-    for (int i = 0; i < 13; i++) {
+    for (int i = 0; i < (half ? 12 : 13); i++) {
         const int c = 13 * half + i;
         int r = c;
         for (int k = 0; k < 12; k++)
@@ -1299,11 +1301,13 @@ constexpr uint64_t comp_word(int half) {
 constexpr uint64_t COMP_LO = comp_word(0), COMP_HI = comp_word(1);
 static_assert((COMP_LO & 31) == 'T' - 'A' && ((COMP_HI >> (5 * ('T' - 'N'))) & 31) == 0, "A <-> T");
 static_assert(((COMP_LO >> (5 * ('K' - 'A'))) & 31) == 'M' - 'A' && (COMP_HI & 31) == 'N' - 'A', "K -> M, N -> N");
+static_assert(((COMP_HI >> (5 * ('Y' - 'N'))) & 31) == 'R' - 'A' && ((COMP_LO >> (5 * ('M' - 'A'))) & 31) == 'K' - 'A',
+              "Y -> R, M -> K: each word's last entry");
 
-// the complement of a sequence byte, case kept; a byte that is no letter is unchanged
+// the complement of a sequence byte, case kept; a byte that is no letter (and 'Z' / 'z') is unchanged
 __device__ __forceinline__ uint32_t comp_ascii(uint32_t c) {
     const uint32_t idx = (c | 0x20u) - 'a';
-    if (idx >= 26u) return c;
+    if (idx >= 25u) return c;
     const uint64_t w = idx < 13u ? COMP_LO : COMP_HI;
     const uint32_t r = (uint32_t)(w >> (5u * (idx < 13u ? idx : idx - 13u))) & 31u;
     return ('A' + r) | (c & 0x20u);

@@ -26,6 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import bytegen  # noqa: E402
 import fuzzgen  # noqa: E402
 import synthlib  # noqa: E402
 
@@ -67,6 +68,24 @@ def run_reference(ref_fa: bytes, tgt_fa: bytes) -> dict:
         return res
 
 
+def byte_cases() -> dict:
+    """Arbitrary byte values and '>' line layouts (tests/bytegen.py): odd bytes shared by both sides in
+    local and global mode, references with several '>' lines, targets whose header is not the first
+    line, and single byte classes placed at every word / lane / tile offset."""
+    cases = {}
+    for i in range(2):
+        cases[f"bytes_local_{i:02d}"] = bytegen.odd_pair(i, 6000, "local")
+        cases[f"bytes_global_{i:02d}"] = bytegen.odd_pair(i, 9000, "global")
+    ref, tgt = bytegen.odd_sequences(900, 14_000, "local")
+    for case in ("many_records", "gt_at_tile", "gt_long_tile"):
+        cases[f"refhdr_{case}"] = (bytegen.ref_layout(ref.tobytes(), case), bytegen.to_fasta(tgt, b">t", 70))
+    for case in ("line69", "odd_bytes", "second_gt"):
+        cases[f"tgthdr_{case}"] = (bytegen.to_fasta(ref, b">r", 70), bytegen.tgt_header_layout(tgt.tobytes(), case))
+    for cls, side in (("tab", "tgt"), ("0xc1", "ref"), ("@", "tgt"), ("n", "tgt")):
+        cases[f"placed_{bytegen.slug(cls)}_{side}"] = bytegen.placed(cls, side)
+    return cases
+
+
 def b64(x: bytes | None):
     return None if x is None else base64.b64encode(x).decode()
 
@@ -82,6 +101,7 @@ def main() -> None:
     for i in range(N_PAREN):
         cases[f"paren_{i:02d}"] = fuzzgen.paren_case(i)
     cases.update(fuzzgen.quirk_cases())
+    cases.update(byte_cases())
     outdir = os.path.join(HERE, "cases")
     os.makedirs(outdir, exist_ok=True)
     force = "--force" in sys.argv

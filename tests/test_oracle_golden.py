@@ -3,7 +3,8 @@
 * every committed fixture (tests/golden/cases, produced by the compiled reference) must be
   reproduced byte-for-byte, including the exit-code behaviour;
 * the larger generator seeds must hash to the reference's sha256 (synth_manifest.json);
-* when oracle/_ref exists (the build container), a wider differential fuzz runs live.
+* when oracle/_ref exists (the build container), a wider differential fuzz runs live, also over
+  arbitrary byte values and '>' line layouts (tests/bytegen.py).
 """
 import hashlib
 import os
@@ -12,6 +13,7 @@ import tempfile
 
 import pytest
 
+import bytegen
 import fuzzgen
 import goldens
 import oraclelib
@@ -104,6 +106,36 @@ def _run_ref_decompress(rec, rfa):
         if p.returncode:
             return p.returncode, None
         return 0, open(os.path.join(d, "o", "reconstructed_genome.fa"), "rb").read()
+
+
+def _byte_case(what, arg):
+    """The inputs of one live byte / layout case; none of them is a committed fixture (other seeds)."""
+    if what in ("odd_local", "odd_global"):
+        return bytegen.odd_pair(arg, 4000 + 977 * (arg % 7), what[4:])
+    if what == "placed":
+        return bytegen.placed(arg[0], arg[1], seed=1)
+    ref, tgt = bytegen.odd_sequences(500 + len(arg), 21_000, "global" if len(arg) % 2 else "local")
+    if what == "ref_layout":
+        return bytegen.ref_layout(ref.tobytes(), arg), bytegen.to_fasta(tgt, b">t", 70)
+    return bytegen.to_fasta(ref, b">r", 70), bytegen.tgt_header_layout(tgt.tobytes(), arg)
+
+
+BYTE_CASES = ([("odd_local", s) for s in range(100, 112)] + [("odd_global", s) for s in range(100, 112)] +
+              [("ref_layout", c) for c in bytegen.REF_LAYOUTS] + [("tgt_layout", c) for c in bytegen.TGT_LAYOUTS] +
+              [("placed", (c, side)) for c in bytegen.CLASSES for side in ("tgt", "ref")])
+
+
+@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (reference sources absent)")
+@pytest.mark.parametrize("what,arg", BYTE_CASES,
+                         ids=[f"{w}-{a if not isinstance(a, tuple) else bytegen.slug(a[0]) + '_' + a[1]}" for w, a in BYTE_CASES])
+def test_byte_differential_vs_reference(what, arg):
+    """Every byte value a FASTA body can hold beside the token punctuation, shared by both sides, and
+    '>' lines anywhere in either file (tests/bytegen.py): the oracle never raises on these, and its
+    record and reconstruction are the compiled reference's."""
+    rfa, tfa = _byte_case(what, arg)
+    rec = oraclelib.compress(rfa, tfa)
+    assert rec == _run_ref(rfa, tfa)
+    assert _run_ref_decompress(rec, rfa) == (0, oraclelib.decompress(rec, rfa))
 
 
 @pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (reference sources absent)")
