@@ -59,7 +59,15 @@ extern "C" {
                                   returned is that un-delta'd text */
 #define SCCG_E_FORMAT       5  /* record file misses a line (decompression.cpp:68-97) */
 #define SCCG_E_RANGE        6  /* token beyond the reference (decompression.cpp:223-229) */
-#define SCCG_E_PARSE        7  /* malformed run line / token (decompression.cpp:309-311) */
+#define SCCG_E_PARSE        7  /* malformed run line / token (decompression.cpp:309-311): text outside
+                                  the decoder's grammar -- integers of an optional sign and at most
+                                  10 digits within int32; run lines of "(d,l)" and bare "d" items
+                                  between ',', starts >= 0, ascending and disjoint, N runs within
+                                  the sequence; every record-line byte outside a "(d,l)" token a
+                                  literal.  Text std::stoi would still read (blanks, trailing junk,
+                                  more digits) and unsorted lowercase runs are reported here too,
+                                  never decoded to other bytes.  Reported before SCCG_E_RANGE
+                                  whatever the order of the faults in the file */
 #define SCCG_E_UNSUPPORTED  8  /* shape outside what sccg_match accepts (see below) */
 #define SCCG_E_INTERNAL     9  /* internal consistency check failed */
 #define SCCG_E_OPEN_REF    10  /* reference FASTA cannot be opened / read (compression.cpp:187-191) */

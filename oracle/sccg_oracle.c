@@ -768,7 +768,10 @@ int orc_decompress(const char* rec, size_t rec_len, const char* ref_fa, size_t r
                 int abs_start = prev_abs + delta;
                 prev_abs = abs_start;
                 if ((long long)abs_start + length > (long long)R.n) { rc = ORC_E_RANGE; goto done; }
-                if (abs_start < 0 || length < 0) { rc = ORC_E_PARSE; goto done; }
+                /* :230 substr(pos > size()) throws std::out_of_range: the numbers parsed, the
+                 * position is outside the reference */
+                if (abs_start < 0) { rc = ORC_E_RANGE; goto done; }
+                if (length < 0) { rc = ORC_E_PARSE; goto done; }
                 sb_put(&dec, R.d + abs_start, (size_t)length);
                 i = (size_t)(ep - enc) + 1;
             } else {

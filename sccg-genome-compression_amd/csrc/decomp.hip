@@ -12,6 +12,22 @@
 // lowercase membership found by binary search over the (sorted, disjoint) run lists.
 // Inputs the reference's own compressor can produce are handled exactly; text outside that
 // grammar is reported as SCCG_E_PARSE instead of reproducing the reference's undefined paths.
+//
+// The grammar (tests/recgen.py states it in full and builds records at each of its edges):
+//   integer      an optional sign and 1 to 10 digits, within int32 (std::stoi also takes leading
+//                blanks, trailing junk and more digits: those are SCCG_E_PARSE here)
+//   run line     "(d,l)" items of at most 25 bytes, l >= 0, a ',' after ')' consumed, and bare "d"
+//                items (runs of one) followed by ',' or the line's end; any number of ',' between,
+//                before and after them; starts (running sums of d) >= 0, ascending and disjoint,
+//                ends within int32; the last N run ends within the sequence, lowercase runs may
+//                pass its end (decompression.cpp:255-262 drops the part beyond)
+//   record line  "(d,l)" tokens; every byte outside one is a literal, ',' digits and ')' included;
+//                p (running sum of d) < 0 or p + l > |R'| is SCCG_E_RANGE
+// Three classes of input follow: inside the grammar the result is the reference's, byte for byte;
+// text the reference defines a result for but the grammar excludes (the stoi leniencies above,
+// descending or overlapping lowercase runs, which it sorts) is SCCG_E_PARSE, never other bytes;
+// what the reference fails on fails here with FORMAT, PARSE or RANGE -- PARSE from any line before
+// RANGE, where the reference reports the first failure in reading order.
 #include <cstdlib>
 
 #include "internal.h"
@@ -102,7 +118,9 @@ __global__ void k_run_items_parse(const uint8_t* __restrict__ s, int64_t n, cons
             while (e < n && is_num(s[e])) e++;
             ok = (e == n || s[e] == ',') && parse_int(s, n, i, e, &d);
         }
-        if (!ok || l < 0) { atomicOr(err, 1); continue; }
+        // (a line of n bytes inside the grammar holds at most n / 2 + 1 items: dc_run_cap; text with
+        // more item starts than that, "((((", is malformed and must not write past the lists)
+        if (!ok || l < 0 || r >= n / 2 + 2) { atomicOr(err, 1); continue; }
         dlt[r] = d;
         len[r] = (int32_t)l;
     }
@@ -379,13 +397,19 @@ __global__ __launch_bounds__(256) void k_rl_write(RlJob j0, RlJob j1, int32_t* _
     int64_t run_cum = tsum[4 * t + 2] + il - tot.lsum;
     int64_t prev_end = rank0 > 0 ? run_start + (prevlen >= 0 ? prevlen : 0) : INT64_MIN;
     bool bad = false;
+    // (the lists hold dc_run_cap(n) = n / 2 + 2 runs, more than a line inside the grammar can have;
+    // every '(' counts as an item start, so malformed text such as "((((" has more: flagged by
+    // pass 1, and nothing is written past the lists)
+    const int64_t cap = n / 2 + 2;
     rl_lane(v, a, inside, nullptr, [&](int64_t, int64_t d, int64_t l, const RlLane& r) {
         const int64_t rank = rank0 + r.cnt;
         const int64_t st = run_start + d;
-        if (st < 0 || st + l > INT32_MAX || (rank > 0 && st < prev_end)) bad = true;
-        start[rank] = (int32_t)st;
-        len[rank] = (int32_t)l;
-        cum[rank] = run_cum;
+        if (st < 0 || st + l > INT32_MAX || (rank > 0 && st < prev_end) || rank >= cap) bad = true;
+        if (rank < cap) {
+            start[rank] = (int32_t)st;
+            len[rank] = (int32_t)l;
+            cum[rank] = run_cum;
+        }
         run_start = st;
         run_cum += l;
         prev_end = st + l;
@@ -416,6 +440,9 @@ __global__ void k_run_finish(const int64_t* __restrict__ dex, const int64_t* __r
 __global__ void k_n_check(const int32_t* __restrict__ ns, const int32_t* __restrict__ nl, const int64_t* __restrict__ d_ncnt,
                           const int64_t* __restrict__ d_D, int32_t* __restrict__ err) {
     const int64_t n = d_ncnt[0];
+    // (a line that failed its parse may count more item starts than the lists hold: PARSE is
+    // reported before this check's bit either way)
+    if (*err & 1) return;
     if (threadIdx.x == 0 && n > 0 && (int64_t)ns[n - 1] + nl[n - 1] > *d_D + d_ncnt[1]) atomicOr(err, 4);
 }
 

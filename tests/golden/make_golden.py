@@ -9,6 +9,10 @@ Writes
   tests/golden/synth_manifest.json    sha256 of the reference's record text / reconstruction
                                       for larger generator seeds (the inputs are regenerated
                                       from tools/synth.c by the tests; only hashes are kept)
+  tests/golden/records.json.gz        (--records: this file alone) the reference's decompression of
+                                      every hand-built record of tests/recgen.py: exit status, sha256
+                                      and length of its FASTA; the inputs too, but for the offset
+                                      sweep, whose records the generator rebuilds (their sha256)
 The reference binaries run with the stub 7z (oracle/stub7z) on PATH; stdout is discarded.
 """
 from __future__ import annotations
@@ -28,6 +32,8 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import bytegen  # noqa: E402
 import fuzzgen  # noqa: E402
+import recgen  # noqa: E402
+import reflib  # noqa: E402
 import synthlib  # noqa: E402
 
 REF_BIN = os.path.join(REPO, "oracle", "_ref")
@@ -90,9 +96,31 @@ def b64(x: bytes | None):
     return None if x is None else base64.b64encode(x).decode()
 
 
+def record_goldens() -> None:
+    """tests/golden/records.json.gz: the compiled reference on every recgen case it defines."""
+    cases = recgen.cases()
+    asked = [c for c in cases if not c.undefined]
+    answers = dict(zip((c.name for c in asked), reflib.run_ref_decompress_many([(c.record, c.ref_fa) for c in asked])))
+    ref_ids = {v: k for k, v in recgen.REFS.items()}
+    doc = {"refs": {k: b64(v) for k, v in recgen.REFS.items()}, "cases": []}
+    for c in cases:
+        rc, fa = answers.get(c.name, (None, None))
+        doc["cases"].append({"name": c.name, "klass": c.klass, "expect": c.expect, "undefined": c.undefined,
+                             "ref": ref_ids[c.ref_fa], "record": None if c.name.startswith("a_off") else b64(c.record),
+                             "record_sha256": hashlib.sha256(c.record).hexdigest(), "rc": rc,
+                             "fasta_sha256": hashlib.sha256(fa).hexdigest() if fa is not None else None,
+                             "fasta_len": len(fa) if fa is not None else None})
+    path = os.path.join(HERE, "records.json.gz")
+    with gzip.GzipFile(path, "wb", mtime=0) as f:
+        f.write(json.dumps(doc, separators=(",", ":")).encode())
+    print(f"records.json.gz: {len(cases)} cases, {len(asked)} answered by the reference, {os.path.getsize(path)} bytes")
+
+
 def main() -> None:
     if not os.path.exists(os.path.join(REF_BIN, "compression")):
         sys.exit("oracle/_ref not built: run `make -C oracle ref` (needs /root/reference)")
+    if "--records" in sys.argv:
+        return record_goldens()
     cases = {}
     for i in range(N_LOCAL):
         cases[f"local_{i:02d}"] = fuzzgen.local_case(i)
@@ -130,6 +158,7 @@ def main() -> None:
         print(manifest[-1])
     with open(os.path.join(HERE, "synth_manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1)
+    record_goldens()
 
 
 if __name__ == "__main__":

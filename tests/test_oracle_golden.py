@@ -17,6 +17,7 @@ import bytegen
 import fuzzgen
 import goldens
 import oraclelib
+import reflib
 import synthlib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,18 +95,7 @@ def test_differential_vs_reference(kind, seed):
     assert oraclelib.compress(rfa, tfa) == _run_ref(rfa, tfa)
 
 
-def _run_ref_decompress(rec, rfa):
-    """decompression <arc> <ref> <out> with the stub 7z (which copies the archive to out/<stem>)."""
-    env = dict(os.environ, PATH=os.path.join(REPO, "oracle", "stub7z") + os.pathsep + os.environ["PATH"])
-    with tempfile.TemporaryDirectory() as d:
-        ap, rp = os.path.join(d, "compressed_genome.txt.7z"), os.path.join(d, "r.fa")
-        open(ap, "wb").write(rec)
-        open(rp, "wb").write(rfa)
-        p = subprocess.run([os.path.join(REF_BIN, "decompression"), ap, rp, os.path.join(d, "o")], env=env,
-                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        if p.returncode:
-            return p.returncode, None
-        return 0, open(os.path.join(d, "o", "reconstructed_genome.fa"), "rb").read()
+_run_ref_decompress = reflib.run_ref_decompress
 
 
 def _byte_case(what, arg):
