@@ -403,6 +403,63 @@ int sccg_cohort_fetch_device(sccg_cohort* cohort, const sccg_cohort_region* regi
                              const sccg_fetch_format* fmt, void* d_out, size_t out_cap /*bytes*/, size_t* out_len /*bytes*/,
                              void* stream);
 
+/* Locate: the inverse of the origin fetch -- where a position of the reference sequence lies in a sample.
+ * A cohort over one shared reference is asked "the window at reference position r in each of these
+ * samples"; with indels upstream r is another sequence position in every one of them.
+ *
+ * For a reader with reference coordinates (sccg_reader_has_coords) let origin(j) be what SCCG_ENC_ORIGIN
+ * returns for sequence position j.  For a reference position r, 0 <= r < |R|, in the coordinates the
+ * origin fetch reports (a position of R, not of R'):
+ *
+ *   copies   the number of sequence positions j with origin(j) == r: the tokens of nonzero length whose
+ *            R' interval holds r
+ *   pos      the smallest such j when copies > 0 -- a sequence position as every fetch takes it (after
+ *            N insertion); it belongs to the first covering token in record order
+ *   pos = SCCG_LOCATE_NONE   no token copies r: the base is deleted in this sample, or the sample
+ *            carries it as a literal; copies 0
+ *   pos = SCCG_LOCATE_REF_N  r lies in a run of uppercase 'N' that the record's R' has erased; copies
+ *            0.  The erased form only: for a record whose N line is "," R' is R and an 'N' is a base
+ *            like any other.
+ *
+ * sccg_reader_enable_locate builds the reader's locate index on the device, once (a second call is a
+ * no-op returning SCCG_OK): the tokens by reference position -- every token start and end sorted, the
+ * number of tokens over each interval between them, and a segment tree of the first token in record
+ * order over each, so a query costs O(log tokens) loads whatever the overlap; at most 44 bytes per
+ * token, in a device allocation of the reader's own that sccg_reader_close frees and that
+ * sccg_reader_device_bytes counts from then on.  SCCG_E_UNSUPPORTED for a reader without reference
+ * coordinates (sccg_last_error says which, as for the origin fetch) or of 2^31 - 1 tokens or R' bases
+ * and more; SCCG_E_NOMEM when the index cannot be allocated -- the reader is then as it was.  A reader
+ * that never calls it allocates and costs what it did.  sccg_reader_can_locate: 1 after it succeeded.
+ *
+ * sccg_reader_locate / _device: pos[i] and, when `copies` is given, copies[i] for ref_pos[i], i < n;
+ * positions may repeat and come in any order.  One copy of the query list, one kernel launch and one
+ * synchronise per call whatever n is; n == 0 is SCCG_OK and writes nothing.  The _device form writes
+ * int64 to d_pos and int32 to d_copies (may be NULL) in device memory, on `stream` (a hipStream_t; NULL
+ * = the context's own).  SCCG_E_INVALID, nothing written, sccg_last_error naming the first offender: a
+ * NULL reader; NULL ref_pos or pos / d_pos with n > 0; d_pos not 8-byte or d_copies not 4-byte aligned;
+ * a ref_pos outside [0, |R|).  SCCG_E_UNSUPPORTED on a reader that has not enabled locating.
+ *
+ * sccg_cohort_locate / _device: locus i is reference position ref_pos of sample `sample`; flags must
+ * be 0.  A cohort's device table is written at sccg_cohort_create, so a reader is locatable through a
+ * cohort only if it had enabled locating BEFORE the cohort was created; enabling it later serves the
+ * reader's own calls and the cohorts created after.  The loci are checked in one pass and the first
+ * offender in list order decides the status and is named: SCCG_E_INVALID for a nonzero flags, a sample
+ * outside [0, n_samples) or a ref_pos outside that sample's [0, |R|); SCCG_E_UNSUPPORTED for a locus
+ * whose sample had not enabled locating.  Everything else as the reader's calls; `copies` / d_copies may
+ * be NULL here too. */
+#define SCCG_LOCATE_NONE  (-1)
+#define SCCG_LOCATE_REF_N (-2)
+typedef struct { int64_t ref_pos; int32_t sample; uint32_t flags /* 0 */; } sccg_cohort_locus;
+int sccg_reader_enable_locate(sccg_reader* reader);
+int sccg_reader_can_locate(const sccg_reader* reader);   /* 1 / 0; 0 for NULL */
+int sccg_reader_locate(sccg_reader* reader, const int64_t* ref_pos /*host*/, size_t n, int64_t* pos /*host, n*/,
+                       int32_t* copies /*host, n; may be NULL*/);
+int sccg_reader_locate_device(sccg_reader* reader, const int64_t* ref_pos /*host*/, size_t n, void* d_pos,
+                              void* d_copies /*may be NULL*/, void* stream);
+int sccg_cohort_locate(sccg_cohort* cohort, const sccg_cohort_locus* loci, size_t n, int64_t* pos, int32_t* copies);
+int sccg_cohort_locate_device(sccg_cohort* cohort, const sccg_cohort_locus* loci /*host*/, size_t n, void* d_pos,
+                              void* d_copies, void* stream);
+
 void sccg_buf_free(sccg_buf* b);
 
 /* Per-kernel device timing with HIP events recorded on the launching stream (process-wide).

@@ -29,7 +29,70 @@ static bool parse_pos(const std::string& s, int64_t* v) {
     return true;
 }
 
+// `fetch --locate <record_file> <reference_file> <refpos>...`: one line per query, `refpos pos copies`
+// tab-separated, 1-based; pos is `-` when no token copies the position and `N` inside an erased N run
+static int locate_main(int argc, char* argv[]) {
+    const bool mixed = argc > 2 && (std::string(argv[2]) == "-i" || std::string(argv[2]) == "--reverse-complement" ||
+                                    std::string(argv[2]) == "--origin");
+    if (argc < 5 || mixed) {
+        std::cerr << "Usage: " << argv[0] << " --locate <record_file> <reference_file> <refpos>...\n"
+                  << "  refpos: a 1-based position of the reference sequence; prints refpos, the first 1-based sequence\n"
+                  << "  position holding a copy of it (- none, N an erased reference N) and the number of copies\n"
+                  << "  --locate is the first argument only, not with -i or --origin\n";
+        return 1;
+    }
+    std::vector<int64_t> q;
+    for (int i = 4; i < argc; i++) {
+        int64_t v = 0;
+        if (!parse_pos(argv[i], &v) || v < 1) {
+            std::cerr << "Error: malformed reference position '" << argv[i] << "' (1-based, decimal)\n";
+            return 1;
+        }
+        q.push_back(v - 1);
+    }
+    std::string ref, rec;
+    if (!slurp(argv[3], ref)) {
+        std::cerr << "Greska pri otvaranju reference: " << argv[3] << "\n";
+        return 1;
+    }
+    if (!slurp(argv[2], rec)) {
+        std::cerr << "Greska pri otvaranju datoteke: " << argv[2] << "\n";
+        return 1;
+    }
+    sccg_ctx* ctx = nullptr;
+    int rc = sccg_ctx_create(cli_device(), &ctx);
+    if (rc) {
+        std::cerr << "Error: no usable GPU (sccg_ctx_create rc=" << rc << ")\n";
+        return 1;
+    }
+    sccg_reference* rf = nullptr;
+    sccg_reader* rd = nullptr;
+    rc = sccg_reference_open(ctx, ref.data(), ref.size(), SCCG_REF_COORDS, &rf);
+    if (!rc) rc = sccg_reader_open_shared(rf, rec.data(), rec.size(), &rd);
+    sccg_reference_close(rf);
+    if (!rc) rc = sccg_reader_enable_locate(rd);
+    std::vector<int64_t> pos(q.size());
+    std::vector<int32_t> copies(q.size());
+    if (!rc) rc = sccg_reader_locate(rd, q.data(), q.size(), pos.data(), copies.data());
+    if (rc) {
+        std::cerr << "Error locating: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_reader_close(rd);
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    std::string out;
+    for (size_t i = 0; i < q.size(); i++)
+        out += std::to_string(q[i] + 1) + "\t" +
+               (pos[i] == SCCG_LOCATE_REF_N ? std::string("N") : pos[i] < 0 ? std::string("-") : std::to_string(pos[i] + 1)) + "\t" +
+               std::to_string(copies[i]) + "\n";
+    std::cout << out;
+    sccg_reader_close(rd);
+    sccg_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
+    if (argc > 1 && std::string(argv[1]) == "--locate") return locate_main(argc, argv);
     const bool rc_flag = argc > 1 && (std::string(argv[1]) == "-i" || std::string(argv[1]) == "--reverse-complement");
     const bool origin = argc > 1 && std::string(argv[1]) == "--origin";
     const int a0 = rc_flag || origin ? 2 : 1;   // the first file argument

@@ -32,6 +32,7 @@
 
 #include "internal.h"
 #include "decomp.h"
+#include "recparse.h"
 
 namespace {
 
@@ -137,16 +138,8 @@ __global__ void k_run_items_parse(const uint8_t* __restrict__ s, int64_t n, cons
 // item, running start, sorted).
 // ---------------------------------------------------------------------------------------------
 constexpr int RL_LANE = 8;   // (16: ~5 us slower on the chr1 reconstruction, more serial bytes per lane)
-constexpr int RL_TILE = 64 * RL_LANE, RL_BEHIND = 32, RL_AHEAD = 64;
+constexpr int RL_TILE = 64 * RL_LANE;   // (RL_BEHIND, RL_AHEAD, RlView, parse_int_v: recparse.h)
 constexpr int RL_STAGE = RL_BEHIND + RL_TILE + RL_AHEAD;
-
-// the wave's staged bytes: global positions [t0 - RL_BEHIND, t0 + tile + RL_AHEAD), 0 outside [0, n)
-struct RlView {
-    const uint8_t* b;
-    int64_t t0, n, tile;
-    __device__ __forceinline__ uint8_t at(int64_t i) const { return b[i - t0 + RL_BEHIND]; }
-    __device__ __forceinline__ int64_t lim() const { return t0 + tile + RL_AHEAD; }
-};
 
 template <int TILE>
 __device__ __forceinline__ RlView rl_stage(const uint8_t* __restrict__ s, int64_t n, int64_t t0, uint8_t* st) {
@@ -156,23 +149,6 @@ __device__ __forceinline__ RlView rl_stage(const uint8_t* __restrict__ s, int64_
     }
     wave_sync();
     return RlView{st, t0, n, TILE};
-}
-
-__device__ __forceinline__ bool parse_int_v(const RlView& v, int64_t a, int64_t e, int64_t* out) {
-    if (a >= e) return false;
-    bool neg = false;
-    if (v.at(a) == '-' || v.at(a) == '+') { neg = v.at(a) == '-'; a++; }
-    if (a >= e || e - a > 10) return false;
-    int64_t x = 0;
-    for (int64_t i = a; i < e; i++) {
-        const uint8_t c = v.at(i);
-        if (c < '0' || c > '9') return false;
-        x = x * 10 + (c - '0');
-    }
-    x = neg ? -x : x;
-    if (x > INT32_MAX || x < INT32_MIN) return false;
-    *out = x;
-    return true;
 }
 
 // one item at i (inside the tile): "(d,l)" or a bare "d" followed by ',' or the end

@@ -34,6 +34,7 @@
 
 #include "decomp.h"
 #include "internal.h"
+#include "locate.h"
 
 static thread_local char g_hip_err[512];
 
@@ -287,6 +288,13 @@ struct sccg_reader {
     bool has_coords = false;    // src.rm turns R' positions into the reference's (the origin fetch)
     std::string header;         // the header line, '>' included, no '\n'; empty: none
     FetchStage stage;
+    int64_t rp_bases = 0;       // |R'|
+    int64_t ref_bases = 0;      // |R|, when has_coords: |R'| plus the N the reference's map has erased
+    // sccg_reader_enable_locate: the index, in an allocation of its own beside `mem`
+    void* loc_mem = nullptr;
+    size_t loc_bytes = 0;
+    bool can_locate = false;
+    LcSrc loc{};
 };
 
 // A cohort (sccg_cohort_create): the device table of its readers' sources, and region staging and a
@@ -297,6 +305,10 @@ struct sccg_cohort {
     std::vector<uint8_t> coords;   // per sample: its reader has reference coordinates
     void* d_tab = nullptr;         // DcCohortEntry per sample
     FetchStage stage;
+    // locate: per sample, |R| when its reader had enabled locating at create (else -1), and the device
+    // table of their LcSrc (null when none had)
+    std::vector<int64_t> ref_bases;
+    void* d_ltab = nullptr;
 };
 
 #define TRY(expr)                                  \
@@ -1542,6 +1554,8 @@ int reader_open_impl(sccg_ctx* ctx, const uint8_t* rfa, int64_t rn, const uint8_
     // reference coordinates: the kept form is R itself; the erased form needs the reference's map
     rd->has_coords = form == REF_KEPT || (ref && ref->coords);
     if (form == REF_ERASED && ref && ref->coords) S.rm = ref->map;
+    rd->rp_bases = nRp;
+    rd->ref_bases = nRp + S.rm.total;
     S.nr = DcRuns{reinterpret_cast<int32_t*>(m + o_ns), reinterpret_cast<int32_t*>(m + o_nl),
                   reinterpret_cast<int64_t*>(m + o_nc), nr.n, nr.total};
     S.lr = DcRuns{reinterpret_cast<int32_t*>(m + o_ls), reinterpret_cast<int32_t*>(m + o_ll), nullptr, lr.n, lr.total};
@@ -1553,6 +1567,7 @@ void reader_free(sccg_reader* rd) {
     if (!rd) return;
     (void)hipSetDevice(rd->ctx->device);
     if (rd->mem) (void)hipFree(rd->mem);
+    if (rd->loc_mem) (void)hipFree(rd->loc_mem);
     rd->stage.free();
     if (rd->ref) reference_drop(rd->ref);
     delete rd;
@@ -1823,6 +1838,7 @@ void cohort_free(sccg_cohort* co) {
     if (!co) return;
     (void)hipSetDevice(co->ctx->device);
     if (co->d_tab) (void)hipFree(co->d_tab);
+    if (co->d_ltab) (void)hipFree(co->d_ltab);
     co->stage.free();
     delete co;
 }
@@ -1850,6 +1866,202 @@ int cohort_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, c
         tot += r.end - r.begin;
     }
     *F = tot;
+    return SCCG_OK;
+}
+
+// -------------------------------------------------------------------------------------------
+// locate (sccg_reader_enable_locate, sccg_*_locate): reference position -> sequence position
+// -------------------------------------------------------------------------------------------
+// The index of locate.h, built in the context's slots (three phases, the token and endpoint counts
+// read between them) and kept in one allocation of the reader's own; the reader is touched only
+// once everything has succeeded.
+// words of the scalar slot (B_SCAL) the build reads back: its token and endpoint counts (the reader's
+// open uses 8-17 and 40, the reference map 24-27)
+constexpr int SC_LOC_NT = 28, SC_LOC_NE = 29;
+int locate_build(sccg_reader* rd) {
+    sccg_ctx* ctx = rd->ctx;
+    hipStream_t s = ctx->stream;
+    const DcFetchSrc& S = rd->src;
+    if (rd->rp_bases >= (int64_t)INT32_MAX)
+        return ctx->fail(SCCG_E_UNSUPPORTED, "the locate index takes a reference form of fewer than 2^31 - 1 bases (this one has %lld)",
+                         (long long)rd->rp_bases);
+    const int64_t nblk = (S.nrec + 63) / 64;
+    GET(int64_t, sc, B_SCAL, 64);
+    int64_t *const d_nt = sc + SC_LOC_NT, *const d_ne = sc + SC_LOC_NE;
+    GET(int64_t, cnt, B_D_CONTRIB, nblk + 1);
+    GET(int64_t, off, B_D_OFF, nblk + 1);
+    GET(int64_t, part, B_PARTIAL2, scan_partials_needed(nblk + 1) + 16);
+    TRY(lc_count_tokens(S, cnt, off, d_nt, part, s));
+    int64_t nt = 0, ne = 0;
+    {
+        const RbItem it{d_nt, &nt, (int)sizeof nt};
+        TRY(dev_readback(&it, 1, s));
+    }
+    if (nt >= (int64_t)INT32_MAX) return ctx->fail(SCCG_E_UNSUPPORTED, "the locate index takes fewer than 2^31 - 1 tokens (the record has %lld)", (long long)nt);
+    LcSrc L{};
+    L.nr = S.nr;
+    L.rm = S.rm;
+    if (nt == 0) {   // a record of literals: nothing to index, every query finds no copy
+        rd->loc = L;
+        rd->can_locate = true;
+        return SCCG_OK;
+    }
+    GET(uint32_t, tp, B_D_LS, nt);
+    GET(int32_t, tl, B_D_LL, nt);
+    GET(int64_t, to, B_D_LC, nt);
+    GET(uint32_t, keys, B_D_NS, 2 * nt);
+    GET(uint32_t, sorted, B_D_NL, 2 * nt);
+    const size_t tmp_bytes = lc_sort_temp_bytes(2 * nt);
+    GET(uint8_t, tmp, B_D_FIDX, tmp_bytes + 16);
+    GET(int64_t, flag, B_D_LP2, 2 * nt + 1);
+    GET(int64_t, rank, B_D_DLT2, 2 * nt + 1);
+    GET(int64_t, part2, B_PARTIAL, scan_partials_needed(2 * nt + 1) + 16);
+    TRY(lc_endpoints(S, off, nt, tp, tl, to, keys, sorted, tmp, tmp_bytes, flag, rank, d_ne, part2, s));
+    {
+        const RbItem it{d_ne, &ne, (int)sizeof ne};
+        TRY(dev_readback(&it, 1, s));
+    }
+    if (ne < 2 || ne > 2 * nt) return ctx->fail(SCCG_E_INTERNAL, "locate index: %lld endpoints for %lld tokens", (long long)ne, (long long)nt);
+    size_t at = 0;
+    auto part_at = [&at](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    const size_t o_tp = part_at((size_t)nt * 4), o_to = part_at((size_t)nt * 8), o_ep = part_at((size_t)ne * 4);
+    const size_t o_cv = part_at((size_t)ne * 4), o_tr = part_at((size_t)ne * 8);
+    const size_t bytes = at + 256;
+    void* mem = nullptr;
+    const hipError_t e = hipMalloc(&mem, bytes);
+    if (e != hipSuccess) return reader_alloc_fail(ctx, e, bytes);
+    uint8_t* m = reinterpret_cast<uint8_t*>(mem);
+    const auto fill = [&]() -> int {
+        HIPTRY(hipMemcpyAsync(m + o_tp, tp, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
+        HIPTRY(hipMemcpyAsync(m + o_to, to, (size_t)nt * 8, hipMemcpyDeviceToDevice, s));
+        TRY(lc_index(tp, tl, nt, sorted, rank, ne, reinterpret_cast<uint32_t*>(m + o_ep), reinterpret_cast<int32_t*>(m + o_cv),
+                     reinterpret_cast<uint32_t*>(m + o_tr), flag, rank, part2, s));
+        HIPTRY(hipStreamSynchronize(s));
+        return SCCG_OK;
+    };
+    const int rc = fill();
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(mem);
+        return rc;
+    }
+    L.ix = LcIndex{reinterpret_cast<const uint32_t*>(m + o_tp), reinterpret_cast<const int64_t*>(m + o_to),
+                   reinterpret_cast<const uint32_t*>(m + o_ep), reinterpret_cast<const int32_t*>(m + o_cv),
+                   reinterpret_cast<const uint32_t*>(m + o_tr), nt, ne};
+    rd->loc = L;
+    rd->loc_mem = mem;
+    rd->loc_bytes = bytes;
+    rd->can_locate = true;
+    return SCCG_OK;
+}
+
+int locate_no_coords(sccg_reader* rd) {
+    return rd->ctx->fail(SCCG_E_UNSUPPORTED,
+                         rd->ref ? "the reader has no reference coordinates: its reference was opened without SCCG_REF_COORDS"
+                                 : "the reader has no reference coordinates: a private reader of a record with an N-run line "
+                                   "(open it through a sccg_reference with SCCG_REF_COORDS)");
+}
+
+// the output pointers' check, the first of every locate entry point (NULL passes: the host forms)
+int locate_align_check(sccg_ctx* ctx, const void* d_pos, const void* d_copies) {
+    if ((uintptr_t)d_pos % 8) return ctx->fail(SCCG_E_INVALID, "d_pos is not aligned to the 8-byte element");
+    if ((uintptr_t)d_copies % 4) return ctx->fail(SCCG_E_INVALID, "d_copies is not aligned to the 4-byte element");
+    return SCCG_OK;
+}
+
+int locate_check(sccg_reader* rd, const int64_t* q, size_t n) {
+    sccg_ctx* ctx = rd->ctx;
+    if (!rd->can_locate) return ctx->fail(SCCG_E_UNSUPPORTED, "the reader has not enabled locating (sccg_reader_enable_locate)");
+    if (!q && n) return ctx->fail(SCCG_E_INVALID, "null query list");
+    for (size_t i = 0; i < n; i++)
+        if (q[i] < 0 || q[i] >= rd->ref_bases)
+            return ctx->fail(SCCG_E_INVALID, "query %zu: reference position %lld is outside the reference [0, %lld)", i, (long long)q[i],
+                             (long long)rd->ref_bases);
+    return SCCG_OK;
+}
+
+int cohort_locate_check(sccg_cohort* co, const sccg_cohort_locus* loci, size_t n) {
+    sccg_ctx* ctx = co->ctx;
+    if (!loci && n) return ctx->fail(SCCG_E_INVALID, "null locus list");
+    const int64_t ns = (int64_t)co->length.size();
+    for (size_t i = 0; i < n; i++) {
+        const sccg_cohort_locus& l = loci[i];
+        if (l.flags) return ctx->fail(SCCG_E_INVALID, "locus %zu has unknown flag bits (flags %u)", i, l.flags);
+        if (l.sample < 0 || l.sample >= ns)
+            return ctx->fail(SCCG_E_INVALID, "locus %zu names sample %d, outside [0, %lld)", i, (int)l.sample, (long long)ns);
+        const int64_t nR = co->ref_bases[(size_t)l.sample];
+        if (nR < 0)
+            return ctx->fail(SCCG_E_UNSUPPORTED, "locus %zu asks sample %d, whose reader had not enabled locating when the cohort "
+                             "was created (sccg_reader_enable_locate before sccg_cohort_create)", i, (int)l.sample);
+        if (l.ref_pos < 0 || l.ref_pos >= nR)
+            return ctx->fail(SCCG_E_INVALID, "locus %zu: reference position %lld is outside sample %d's reference [0, %lld)", i,
+                             (long long)l.ref_pos, (int)l.sample, (long long)nR);
+    }
+    return SCCG_OK;
+}
+
+// The two query lists a locate call is read from.
+struct ReaderLoci {
+    static constexpr bool samples = false;
+    const int64_t* q;
+    int64_t pos(size_t i) const { return q[i]; }
+    int32_t sample(size_t) const { return 0; }
+};
+struct CohortLoci {
+    static constexpr bool samples = true;
+    const sccg_cohort_locus* l;
+    int64_t pos(size_t i) const { return l[i].ref_pos; }
+    int32_t sample(size_t i) const { return l[i].sample; }
+};
+
+// Queries validated, n > 0.  ONE pinned image -- the n reference positions, then, for a cohort, the
+// samples as int32 -- in one copy; one launch; one sync.  d_pos given: the device forms, results
+// straight to the caller's memory.  Else the host forms: results into the stage's own device output
+// and, behind the launch, into the image's tail, copied out after the one sync.
+template <typename Loci>
+int locate_run(sccg_ctx* ctx, FetchStage& st, const Loci& loci, size_t n, LcLocate c, void* d_pos, void* d_copies, int64_t* h_pos,
+               int32_t* h_copies, hipStream_t s) {
+    constexpr bool samples = Loci::samples;
+    HIPTRY(hipSetDevice(ctx->device));
+    const size_t n4 = (n * sizeof(int32_t) + 7) & ~(size_t)7;
+    const size_t in_bytes = n * sizeof(int64_t) + (samples ? n4 : 0), out_bytes = d_pos ? 0 : n * sizeof(int64_t) + n4;
+    size_t cap = 0;
+    hipError_t e = st.reserve_regions(in_bytes + out_bytes, &cap);
+    if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
+    if (!d_pos) {
+        e = st.reserve_out(out_bytes, &cap);
+        if (e != hipSuccess) return reader_alloc_fail(ctx, e, cap);
+        d_pos = st.d_out;
+        d_copies = h_copies ? reinterpret_cast<uint8_t*>(st.d_out) + n * sizeof(int64_t) : nullptr;
+    }
+    int64_t* h = st.h_reg;
+    int32_t* hs = reinterpret_cast<int32_t*>(h + n);
+    for (size_t i = 0; i < n; i++) {
+        h[i] = loci.pos(i);
+        if (samples) hs[i] = loci.sample(i);
+    }
+    int64_t* d = reinterpret_cast<int64_t*>(st.d_reg);
+    HIPTRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    c.d_q = d;
+    c.d_samp = samples ? reinterpret_cast<const int32_t*>(d + n) : nullptr;
+    c.n = (int64_t)n;
+    c.d_pos = reinterpret_cast<int64_t*>(d_pos);
+    c.d_copies = reinterpret_cast<int32_t*>(d_copies);
+    TRY(lc_locate(c, s));
+    uint8_t* back = reinterpret_cast<uint8_t*>(h) + in_bytes;
+    if (h_pos) {
+        HIPTRY(hipMemcpyAsync(back, d_pos, n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        if (h_copies) HIPTRY(hipMemcpyAsync(back + n * sizeof(int64_t), d_copies, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIPTRY(hipStreamSynchronize(s));
+    if (h_pos) {
+        memcpy(h_pos, back, n * sizeof(int64_t));
+        if (h_copies) memcpy(h_copies, back + n * sizeof(int64_t), n * sizeof(int32_t));
+    }
     return SCCG_OK;
 }
 
@@ -2107,7 +2319,7 @@ int sccg_reader_open_shared(sccg_reference* ref, const char* rec_text, size_t re
     return reader_open(ctx, nullptr, 0, drc, (int64_t)rec_len, out, ref);
 }
 
-size_t sccg_reader_device_bytes(const sccg_reader* reader) { return reader ? reader->mem_bytes : 0; }
+size_t sccg_reader_device_bytes(const sccg_reader* reader) { return reader ? reader->mem_bytes + reader->loc_bytes : 0; }
 
 int sccg_cohort_create(sccg_reader* const* readers, size_t n_samples, sccg_cohort** out) {
     if (out) *out = nullptr;
@@ -2142,6 +2354,31 @@ int sccg_cohort_create(sccg_reader* const* readers, size_t n_samples, sccg_cohor
         cohort_free(co);
         return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__));
     }
+    // the locate table, when a reader has enabled locating: what each of them reads, as of now
+    std::vector<LcSrc> ltab(n_samples);
+    co->ref_bases.assign(n_samples, -1);
+    bool any = false;
+    for (size_t i = 0; i < n_samples; i++) {
+        ltab[i].ix.nt = -1;
+        if (!readers[i]->can_locate) continue;
+        ltab[i] = readers[i]->loc;
+        co->ref_bases[i] = readers[i]->ref_bases;
+        any = true;
+    }
+    if (any) {
+        const size_t lbytes = n_samples * sizeof(LcSrc);
+        e = hipMalloc(&co->d_ltab, lbytes);
+        if (e != hipSuccess) {
+            co->d_ltab = nullptr;
+            cohort_free(co);
+            return reader_alloc_fail(ctx, e, lbytes);
+        }
+        e = hipMemcpy(co->d_ltab, ltab.data(), lbytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            cohort_free(co);
+            return ctx->hipfail(sccg_hip_fail(e, "hipMemcpy", __FILE__, __LINE__));
+        }
+    }
     *out = co;
     return SCCG_OK;
 }
@@ -2171,6 +2408,68 @@ int sccg_cohort_fetch(sccg_cohort* cohort, const sccg_cohort_region* regions, si
     if (rc) return rc;   // (nothing written: *out is the caller's as it was)
     return fetch_to_host(cohort->ctx, cohort->stage, CohortRegions{regions}, n, fetch_call(nullptr, cohort->d_tab, fmt, fmt->flags),
                          (size_t)F * bpb, out);
+}
+
+int sccg_reader_enable_locate(sccg_reader* reader) {
+    if (!reader) return SCCG_E_INVALID;
+    if (reader->can_locate) return SCCG_OK;
+    if (!reader->has_coords) return locate_no_coords(reader);
+    sccg_ctx* ctx = reader->ctx;
+    HIPTRY(hipSetDevice(ctx->device));
+    const int rc = locate_build(reader);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);   // (nothing of the failed build is still queued)
+    return rc;
+}
+
+int sccg_reader_can_locate(const sccg_reader* reader) { return reader && reader->can_locate ? 1 : 0; }
+
+int sccg_reader_locate_device(sccg_reader* reader, const int64_t* ref_pos, size_t n, void* d_pos, void* d_copies, void* stream) {
+    if (!reader) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    if (!d_pos && n) return ctx->fail(SCCG_E_INVALID, "null d_pos");
+    int rc = locate_align_check(ctx, d_pos, d_copies);
+    if (!rc) rc = locate_check(reader, ref_pos, n);
+    if (rc || !n) return rc;
+    LcLocate c{};
+    c.src = &reader->loc;
+    return locate_run(ctx, reader->stage, ReaderLoci{ref_pos}, n, c, d_pos, d_copies, nullptr, nullptr,
+                      stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sccg_reader_locate(sccg_reader* reader, const int64_t* ref_pos, size_t n, int64_t* pos, int32_t* copies) {
+    if (!reader) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    if (!pos && n) return ctx->fail(SCCG_E_INVALID, "null pos");
+    const int rc = locate_check(reader, ref_pos, n);
+    if (rc || !n) return rc;
+    LcLocate c{};
+    c.src = &reader->loc;
+    return locate_run(ctx, reader->stage, ReaderLoci{ref_pos}, n, c, nullptr, nullptr, pos, copies, ctx->stream);
+}
+
+int sccg_cohort_locate_device(sccg_cohort* cohort, const sccg_cohort_locus* loci, size_t n, void* d_pos, void* d_copies,
+                              void* stream) {
+    if (!cohort) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    if (!d_pos && n) return ctx->fail(SCCG_E_INVALID, "null d_pos");
+    int rc = locate_align_check(ctx, d_pos, d_copies);
+    if (!rc) rc = cohort_locate_check(cohort, loci, n);
+    if (rc || !n) return rc;
+    LcLocate c{};
+    c.d_tab = reinterpret_cast<const LcSrc*>(cohort->d_ltab);
+    return locate_run(ctx, cohort->stage, CohortLoci{loci}, n, c, d_pos, d_copies, nullptr, nullptr,
+                      stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int sccg_cohort_locate(sccg_cohort* cohort, const sccg_cohort_locus* loci, size_t n, int64_t* pos, int32_t* copies) {
+    if (!cohort) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    if (!pos && n) return ctx->fail(SCCG_E_INVALID, "null pos");
+    const int rc = cohort_locate_check(cohort, loci, n);
+    if (rc || !n) return rc;
+    LcLocate c{};
+    c.d_tab = reinterpret_cast<const LcSrc*>(cohort->d_ltab);
+    return locate_run(ctx, cohort->stage, CohortLoci{loci}, n, c, nullptr, nullptr, pos, copies, ctx->stream);
 }
 
 // match_sequences seam (compression.cpp:36): local segments or the windowed global walk

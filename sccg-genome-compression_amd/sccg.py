@@ -25,6 +25,8 @@ REF_FORMS = {"erased": 1, "kept": 2}                       # SCCG_REF_*: which R
 REF_COORDS = 4                                             # SCCG_REF_COORDS: keep the R' -> R map (origin fetch)
 ENCODINGS = {"ascii": 0, "index": 1, "onehot": 2, "origin": 3}     # SCCG_ENC_*
 DTYPES = {"u8": 0, "f16": 1, "bf16": 2, "f32": 3, "i32": 4}        # SCCG_DT_* ("i32": with "origin" only)
+LOCATE_NONE = -1       # SCCG_LOCATE_NONE: no token copies the reference position (deleted, or a literal)
+LOCATE_REF_N = -2      # SCCG_LOCATE_REF_N: the position lies in an N run of the reference that R' has erased
 ORIGIN_LITERAL, ORIGIN_N = -1, -2                          # "origin" values that are no reference position
 ERRORS = {1: "SCCG_E_INVALID", 2: "SCCG_E_HIP", 3: "SCCG_E_NOMEM", 4: "SCCG_E_DELTA_STOI",
           5: "SCCG_E_FORMAT", 6: "SCCG_E_RANGE", 7: "SCCG_E_PARSE", 8: "SCCG_E_UNSUPPORTED",
@@ -68,6 +70,11 @@ class Region(ctypes.Structure):
 class CohortRegion(ctypes.Structure):
     """sccg_cohort_region: a region of one sample; flags bit 0 = reverse strand."""
     _fields_ = [("begin", ctypes.c_int64), ("end", ctypes.c_int64), ("sample", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class CohortLocus(ctypes.Structure):
+    """sccg_cohort_locus: a position of the reference sequence, asked of one sample; flags 0."""
+    _fields_ = [("ref_pos", ctypes.c_int64), ("sample", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class FetchFormat(ctypes.Structure):
@@ -188,6 +195,14 @@ def load_library():
         lib.sccg_cohort_fetch.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, ctypes.POINTER(FetchFormat), ctypes.POINTER(Buf)]
         lib.sccg_cohort_fetch_device.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, ctypes.POINTER(FetchFormat), vp, sz,
                                                  ctypes.POINTER(sz), vp]
+    if hasattr(lib, "sccg_reader_enable_locate"):   # (absent from builds older than locate: A/B runs)
+        i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64)
+        lib.sccg_reader_enable_locate.argtypes = [vp]
+        lib.sccg_reader_can_locate.argtypes = [vp]
+        lib.sccg_reader_locate.argtypes = [vp, i64p, sz, i64p, i32p]
+        lib.sccg_reader_locate_device.argtypes = [vp, i64p, sz, vp, vp, vp]
+        lib.sccg_cohort_locate.argtypes = [vp, ctypes.POINTER(CohortLocus), sz, i64p, i32p]
+        lib.sccg_cohort_locate_device.argtypes = [vp, ctypes.POINTER(CohortLocus), sz, vp, vp, vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -648,6 +663,44 @@ class Reader:
             out = out.view(len(regions), lens.pop(), *shape[1:])
         return out
 
+    def enable_locate(self) -> None:
+        """Build the locate index on the device (sccg_reader_enable_locate; a second call does
+        nothing).  Needs has_coords.  Enable it before the reader joins a Cohort that is to locate in it."""
+        rc = self.lib.sccg_reader_enable_locate(self.ptr)
+        if rc:
+            self.ctx._err(rc)
+
+    @property
+    def can_locate(self) -> bool:
+        return bool(self.lib.sccg_reader_can_locate(self.ptr))
+
+    def locate(self, ref_positions):
+        """(pos int64 [n], copies int32 [n]) for 0-based positions of the reference sequence: the first
+        sequence position a token copied each from (LOCATE_NONE: none; LOCATE_REF_N: an erased N of the
+        reference) and how many sequence positions hold a copy.  One launch per call."""
+        import numpy as np
+        q = np.ascontiguousarray(ref_positions, dtype=np.int64).reshape(-1)
+        pos, copies = np.empty(q.size, dtype=np.int64), np.empty(q.size, dtype=np.int32)
+        i64p, i32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+        rc = self.lib.sccg_reader_locate(self.ptr, q.ctypes.data_as(i64p), q.size, pos.ctypes.data_as(i64p), copies.ctypes.data_as(i32p))
+        if rc:
+            self.ctx._err(rc)
+        return pos, copies
+
+    def locate_tensor(self, ref_positions, stream=None):
+        """locate() into torch tensors on the context's device: (pos int64 [n], copies int32 [n])."""
+        import numpy as np
+        import torch
+        q = np.ascontiguousarray(ref_positions, dtype=np.int64).reshape(-1)
+        dev = torch.device("cuda", self.ctx.device)
+        pos, copies = torch.empty(q.size, dtype=torch.int64, device=dev), torch.empty(q.size, dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        rc = self.lib.sccg_reader_locate_device(self.ptr, q.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), q.size,
+                                                pos.data_ptr() or None, copies.data_ptr() or None, s.cuda_stream or None)
+        if rc:
+            self.ctx._err(rc)
+        return pos, copies
+
 
 class Cohort:
     """sccg_cohort: the encoded fetch over many readers of one context, each region naming its sample,
@@ -744,3 +797,58 @@ class Cohort:
         if len(lens) == 1 and items:
             out = out.view(len(items), lens.pop(), *shape[1:])
         return out
+
+    @staticmethod
+    def _loci(items):
+        """(sample, ref_pos) -> sccg_cohort_locus array."""
+        rows = [(int(r), int(s), 0) for s, r in items]
+        return rows, ((CohortLocus * len(rows))(*rows) if rows else None)
+
+    def locate(self, items):
+        """Reader.locate over the cohort (sccg_cohort_locate): items (sample, ref_pos) -> (pos int64 [n],
+        copies int32 [n]), one launch.  A sample answers only if its reader had enable_locate() called
+        before this cohort was created."""
+        import numpy as np
+        rows, arr = self._loci(items)
+        pos, copies = np.empty(len(rows), dtype=np.int64), np.empty(len(rows), dtype=np.int32)
+        rc = self.lib.sccg_cohort_locate(self.ptr, arr, len(rows), pos.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                         copies.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        if rc:
+            self.ctx._err(rc)
+        return pos, copies
+
+    def locate_tensor(self, items, stream=None):
+        """locate() into torch tensors on the context's device."""
+        import torch
+        rows, arr = self._loci(items)
+        dev = torch.device("cuda", self.ctx.device)
+        pos, copies = torch.empty(len(rows), dtype=torch.int64, device=dev), torch.empty(len(rows), dtype=torch.int32, device=dev)
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        rc = self.lib.sccg_cohort_locate_device(self.ptr, arr, len(rows), pos.data_ptr() or None, copies.data_ptr() or None,
+                                                s.cuda_stream or None)
+        if rc:
+            self.ctx._err(rc)
+        return pos, copies
+
+    def fetch_tensor_at(self, items, length: int, encoding: str = "onehot", dtype=None, revcomp: bool = False):
+        """The window of `length` bases that starts where reference position ref_pos lies in each sample:
+        items (sample, ref_pos) -> (tensor [n, length] or [n, length, 4] as fetch_tensor gives it, found
+        bool [n]).  A row is zero and not found when the position has no copy in the sample (locate()'s
+        negative answers) or the window would pass the sample's end.  One locate and one fetch launch."""
+        import torch
+        items = [(int(s), int(r)) for s, r in items]
+        length = int(length)
+        if length <= 0:
+            raise ValueError("fetch_tensor_at: length must be positive")
+        pos, _ = self.locate(items)
+        found = [p >= 0 and p + length <= self.readers[s].length for (s, _), p in zip(items, pos.tolist())]
+        windows = [(s, int(p), int(p) + length) for (s, _), p, f in zip(items, pos.tolist(), found) if f]
+        dev = torch.device("cuda", self.ctx.device)
+        mask = torch.tensor(found, dtype=torch.bool, device=dev)
+        if len(windows) == len(items) and items:
+            return self.fetch_tensor(windows, encoding, dtype, revcomp), mask
+        got = self.fetch_tensor(windows, encoding, dtype, revcomp)   # (none found: the empty fetch, for its dtype checks)
+        out = torch.zeros((len(items), length) + ((4,) if encoding == "onehot" else ()), dtype=got.dtype, device=dev)
+        if windows:
+            out[mask] = got.view(len(windows), length, *out.shape[2:])
+        return out, mask

@@ -23,7 +23,10 @@ open times, private against shared.  Then the origin fetch (SCCG_ENC_ORIGIN, 4 b
 read) beside index (1 byte) and one-hot u8 (the same 4 bytes, R' read) at the same two shapes, one
 reader and the S-sample cohort, all through a reference opened with SCCG_REF_COORDS and interleaved
 call by call; and sccg_reference_open_device with and without SCCG_REF_COORDS.  --only-origin runs
-that last section alone.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
+that last section alone.  --only-locate runs the locate leg alone: sccg_reader_enable_locate (host ms, index
+bytes), sccg_reader_locate_device and sccg_cohort_locate_device for 1 / 1,000 / 100,000 random reference
+positions (every located base checked against the reference), the 1000 x 1 kb index and origin fetches
+of the same run, and Cohort.fetch_tensor_at beside the fetch_tensor it wraps.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
 must name the reference base the target's base is, -2 an N).  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
@@ -254,6 +257,102 @@ def origin_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec,
     return out
 
 
+def locate_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, rec_len, truth, rfa, S=8):
+    """enable_locate (time, index bytes, tokens); locate of 1 / 1,000 / 100,000 random reference positions, one
+    reader and the S-sample cohort, beside the 1000 x 1 kb index and origin fetches of the same run;
+    fetch_tensor_at for 1000 x 1 kb against the fetch_tensor it wraps.  HIP events around the device calls."""
+    s = stream.cuda_stream
+    out = {"samples": S, "same_record": True}
+    ref = ctx.open_reference_device(d_ref.data_ptr(), ref_len, stream=s, coords=True)
+    readers = [ref.open_reader_device(d_rec.data_ptr(), rec_len, s) for _ in range(S)]
+    ts, before = [], readers[0].device_bytes
+    for r in readers:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r.enable_locate()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    rd, co = readers[0], sccg.Cohort(readers)
+    out["enable_locate_ms"] = spread(ts)
+    out["index_bytes"] = rd.device_bytes - before
+    out["reader_bytes_before"] = before
+    nR = len(rfa.partition(b"\n")[2].replace(b"\n", b""))
+    Ru = np.frombuffer(rfa.partition(b"\n")[2].replace(b"\n", b"").upper(), dtype=np.uint8)
+    Tu = np.frombuffer(truth.upper(), dtype=np.uint8)
+    rng = random.Random(5)
+
+    def events(call):
+        ev = []
+        for i in range(a.warmup + a.calls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            stream.synchronize()
+            e0.record(stream)
+            call()
+            e1.record(stream)
+            stream.synchronize()
+            if i >= a.warmup:
+                ev.append(e0.elapsed_time(e1))
+        return ev
+
+    def kernel(call):
+        ctx.profile(True, families=["fetch"])
+        for _ in range(a.calls):
+            call()
+        t = ctx.profile_get().get("fetch", (0.0, 0))
+        ctx.profile(False)
+        return round(t[0] / max(t[1], 1), 4), t[1] / a.calls
+
+    out["locate"] = {}
+    for n in (1, 1000, 100_000):
+        q = [rng.randrange(nR) for _ in range(n)]
+        qa = (ctypes.c_int64 * n)(*q)
+        loci = (sccg.CohortLocus * n)(*[(r, k % S, 0) for k, r in enumerate(q)])
+        d_pos = torch.empty(n, dtype=torch.int64, device=dev)
+        d_cp = torch.empty(n, dtype=torch.int32, device=dev)
+
+        def reader_call():
+            assert lib.sccg_reader_locate_device(rd.ptr, qa, n, d_pos.data_ptr(), d_cp.data_ptr(), s) == 0
+
+        def cohort_call():
+            assert lib.sccg_cohort_locate_device(co.ptr, loci, n, d_pos.data_ptr(), d_cp.data_ptr(), s) == 0
+
+        for who, call in (("reader", reader_call), ("cohort", cohort_call)):
+            ev = events(call)
+            km, lpc = kernel(call)
+            pos, cp = d_pos.cpu().numpy(), d_cp.cpu().numpy()
+            hit = pos >= 0
+            qn = np.array(q, dtype=np.int64)
+            exact = bool(np.array_equal(Tu[pos[hit]], Ru[qn[hit]]) and np.all(cp[hit] >= 1) and np.all(cp[~hit] == 0))
+            out["locate"][f"{n}/{who}"] = {"event_ms": spread(ev), "kernel_ms_mean": km, "launches_per_call": lpc,
+                                          "found": round(float(hit.mean()), 4), "max_copies": int(cp.max()), "exact": exact}
+    # the yardsticks of the same run: 1000 x 1 kb index and origin fetches, and fetch_tensor_at beside fetch_tensor
+    L, n, ln = rd.length, 1000, 1000
+    begins = [rng.randrange(L - ln) for _ in range(n)]
+    flat = (sccg.Region * n)(*[(b, b + ln) for b in begins])
+    got = ctypes.c_size_t()
+    out["fetch"] = {}
+    for row, (enc, dt, bpb) in {"index": ("index", "u8", 1), "origin": ("origin", "i32", 4)}.items():
+        fmt = sccg.FetchFormat(sccg.ENCODINGS[enc], sccg.DTYPES[dt], 0, 0)
+        d_o = torch.empty(n * ln * bpb + 64, dtype=torch.uint8, device=dev)
+
+        def call():
+            assert lib.sccg_reader_fetch_encoded_device(rd.ptr, flat, n, None, ctypes.byref(fmt), d_o.data_ptr(), n * ln * bpb,
+                                                        ctypes.byref(got), s) == 0
+
+        ev = events(call)
+        out["fetch"][f"1000x1kb/{row}/reader"] = {"event_ms": spread(ev), "kernel_ms_mean": kernel(call)[0]}
+    items = [(k % S, rng.randrange(nR)) for k in range(n)]
+    pos, _ = co.locate(items)
+    windows = [(sm, int(p), int(p) + ln) for (sm, _), p in zip(items, pos.tolist()) if p >= 0 and p + ln <= L]
+    ev_at = events(lambda: co.fetch_tensor_at(items, ln, "index"))
+    ev_ft = events(lambda: co.fetch_tensor(windows, "index"))
+    out["fetch_tensor_at"] = {"items": n, "found": len(windows), "at_event_ms": spread(ev_at), "fetch_tensor_event_ms": spread(ev_ft)}
+    co.close()
+    for r in readers:
+        r.close()
+    ref.close()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", default="hg")
@@ -263,6 +362,7 @@ def main() -> None:
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only-origin", action="store_true", help="the origin section alone")
+    ap.add_argument("--only-locate", action="store_true", help="the locate section alone")
     a = ap.parse_args()
     import torch
     import sccg
@@ -299,6 +399,15 @@ def main() -> None:
     code = [4] * 256
     for k, ch in enumerate(b"ACGT"):
         code[ch] = code[ch + 32] = k
+    if a.only_locate:
+        loc = locate_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth, rfa)
+        loc["record_line_tokens"] = rec_h.rstrip(b"\n").rpartition(b"\n")[2].count(b"(")   # (zero-length ones included)
+        out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls, "locate": loc}
+        ctx.close()
+        print(json.dumps(out))
+        if not all(v["exact"] for v in loc["locate"].values()):
+            raise SystemExit("bench_fetch: locate section: a located base is not the reference's")
+        return
     if a.only_origin:
         out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
                "origin": origin_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth, rfa, code)}
