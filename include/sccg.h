@@ -34,6 +34,9 @@
  * sccg_cohort_create / _fetch /       the encoded fetch over many records of one context, each region
  *   _fetch_device (sccg_cohort_close,   naming its record, in one launch (no counterpart)
  *    _samples)
+ * sccg_reader_segments / _device,     a region's alignment to the reference, run-length coded: the gapless
+ *   sccg_cohort_segments / _device      blocks, literals and N runs the origin fetch spells out per base
+ *                                       (no counterpart)
  *
  * Conventions: status ints (0 = OK); the library never calls exit(); host buffers it returns are
  * malloc'ed and released with sccg_buf_free.  One context per GPU; a context is not re-entrant;
@@ -459,6 +462,48 @@ int sccg_reader_locate_device(sccg_reader* reader, const int64_t* ref_pos /*host
 int sccg_cohort_locate(sccg_cohort* cohort, const sccg_cohort_locus* loci, size_t n, int64_t* pos, int32_t* copies);
 int sccg_cohort_locate_device(sccg_cohort* cohort, const sccg_cohort_locus* loci /*host*/, size_t n, void* d_pos,
                               void* d_copies, void* stream);
+
+/* Segments: a region's alignment to the reference, run-length coded -- the gapless blocks where the
+ * sample follows the reference, and the literals and N runs between them.  What the origin fetch says with
+ * 4 bytes per base, this says with 24 bytes per segment, and its work is in proportion to the record-line
+ * bytes under the regions, not to their bases.
+ *
+ * For a reader with reference coordinates (sccg_reader_has_coords) let origin(j) be what SCCG_ENC_ORIGIN
+ * returns for sequence position j.  A segment of region [begin, end) is a maximal interval [a, b) inside
+ * it such that for every j in [a, b - 1) origin(j) >= 0 and origin(j + 1) == origin(j) + 1, or both are
+ * -1, or both are -2; it is reported as {pos = a, len = b - a, ref = origin(a)}.  The segments of a region
+ * tile it exactly, in ascending pos; an empty region has none; they are clipped to the region, so ref
+ * belongs to the first base inside it.  The definition speaks of bases, never of tokens: a token that
+ * starts where the one before it ends, on the reference too, continues its segment (zero-length tokens
+ * between them change nothing); a token is split by a target N run put into it, and where its interval of
+ * R' crosses an erased run of 'N' in R (the origin jumps there); touching N runs of the target form one
+ * -2 segment.
+ *
+ * The segments of region i are out[off[i], off[i + 1]), off[0] == 0, off[n] the total; regions may be
+ * empty, repeat, overlap and come in any order; n == 0 is SCCG_OK with no segments (off[0] = 0).  The
+ * host forms return the sccg_segment array in *out (out->len bytes; sccg_buf_free) and, when `off` is
+ * given, the n + 1 offsets.  The _device forms write int64 offsets to d_off (may be NULL) and segments
+ * to d_seg, device memory, on `stream` (a hipStream_t; NULL = the context's own): d_seg == NULL is a size
+ * query that only sets *n_seg; with cap (in segments) too small they return SCCG_E_NOMEM, *n_seg the number
+ * needed, the buffers' contents unspecified.  Forward strand only.  Six kernel launches and one host read
+ * (the total) per call, whatever n, the region sizes and the samples touched are (four for a size query).
+ * The locate index is not needed.
+ *
+ * SCCG_E_INVALID, nothing written, sccg_last_error naming the first offender: a NULL reader / cohort /
+ * out / n_seg; a NULL region list with n > 0; d_off or d_seg not 8-byte aligned; a region outside 0 <=
+ * begin <= end <= length; in a cohort a sample outside [0, n_samples) or ANY flag bit set, bit 0 included.
+ * SCCG_E_UNSUPPORTED, the size query included: a reader without reference coordinates; in a cohort the
+ * regions are checked in one pass and the first offender in list order decides the status.  Both forms
+ * synchronise before returning. */
+typedef struct { int64_t pos, len, ref; } sccg_segment;   /* ref >= 0, -1 literal, -2 target N run */
+int sccg_reader_segments(sccg_reader* reader, const sccg_region* regions, size_t n, int64_t* off /*host, n + 1; may be NULL*/,
+                         sccg_buf* out /*sccg_segment[]*/);
+int sccg_reader_segments_device(sccg_reader* reader, const sccg_region* regions /*host*/, size_t n,
+                                void* d_off /*int64[n + 1] or NULL*/, void* d_seg, size_t cap /*segments*/, size_t* n_seg,
+                                void* stream);
+int sccg_cohort_segments(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, int64_t* off, sccg_buf* out);
+int sccg_cohort_segments_device(sccg_cohort* cohort, const sccg_cohort_region* regions /*host*/, size_t n, void* d_off, void* d_seg,
+                                size_t cap, size_t* n_seg, void* stream);
 
 void sccg_buf_free(sccg_buf* b);
 

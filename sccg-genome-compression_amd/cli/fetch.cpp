@@ -8,7 +8,7 @@
 // complemented, as `samtools faidx -i` does, with `/rc` appended to its header line.  Exit code 1 on
 // usage / region / open / format errors; the regions are parsed before the GPU is touched.
 // `fetch --origin <record_file> <reference_file> <region>...` (first argument only) prints, per
-// region, the usual header line and then where its bases come from (SCCG_ENC_ORIGIN, through a
+// region, the usual header line and then where its bases come from (sccg_reader_segments, through a
 // reference opened with SCCG_REF_COORDS): one tab-separated line per maximal run, everything 1-based
 // and inclusive -- `tbegin tend rbegin rend` for bases copied from consecutively ascending reference
 // positions, `tbegin tend *` for literals of the record line, `tbegin tend N` for bases of the target's
@@ -150,9 +150,9 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     sccg_buf seq{};
-    if (origin) {
-        const sccg_fetch_format fmt{SCCG_ENC_ORIGIN, SCCG_DT_I32, 0, 0};
-        rc = sccg_reader_fetch_encoded(rd, regions.data(), regions.size(), nullptr, &fmt, &seq);
+    std::vector<int64_t> seg_off(regions.size() + 1);
+    if (origin) {   // the maximal runs themselves: seq holds sccg_segment[]
+        rc = sccg_reader_segments(rd, regions.data(), regions.size(), seg_off.data(), &seq);
     } else if (rc_flag) {
         const sccg_fetch_format fmt{SCCG_ENC_ASCII, SCCG_DT_U8, SCCG_FETCH_REVCOMP, 0};
         rc = sccg_reader_fetch_encoded(rd, regions.data(), regions.size(), nullptr, &fmt, &seq);
@@ -169,24 +169,20 @@ int main(int argc, char* argv[]) {
     const char* hdr = sccg_reader_header(rd, &hlen);
     const std::string name = hlen > 1 ? std::string(hdr + 1, hlen - 1) : std::string("seq");
     std::string out;
-    size_t at = 0;
+    size_t at = 0, ri = 0;
     for (const sccg_region& r : regions) {
         out += ">" + name + ":" + std::to_string(r.begin + 1) + "-" + std::to_string(r.end) + (rc_flag ? "/rc\n" : "\n");
         const size_t len = (size_t)(r.end - r.begin);
         if (origin) {   // maximal runs: ascending reference positions, literals, N
-            const char* o4 = seq.data + 4 * at;
-            auto val = [o4](size_t k) { int32_t v; memcpy(&v, o4 + 4 * k, 4); return v; };
-            for (size_t k = 0; k < len;) {
-                const int32_t v = val(k);
-                size_t e = k + 1;
-                while (e < len && (v >= 0 ? val(e) == v + (int32_t)(e - k) : val(e) == v)) e++;
-                out += std::to_string(r.begin + 1 + (int64_t)k) + "\t" + std::to_string(r.begin + (int64_t)e) + "\t";
-                if (v >= 0) out += std::to_string((int64_t)v + 1) + "\t" + std::to_string((int64_t)v + (int64_t)(e - k));
-                else out += v == -1 ? "*" : "N";
+            for (int64_t k = seg_off[ri]; k < seg_off[ri + 1]; k++) {
+                sccg_segment g;
+                memcpy(&g, seq.data + (size_t)k * sizeof g, sizeof g);
+                out += std::to_string(g.pos + 1) + "\t" + std::to_string(g.pos + g.len) + "\t";
+                if (g.ref >= 0) out += std::to_string(g.ref + 1) + "\t" + std::to_string(g.ref + g.len);
+                else out += g.ref == -1 ? "*" : "N";
                 out += '\n';
-                k = e;
             }
-            at += len;
+            ri++;
             continue;
         }
         for (size_t k = 0; k < len; k += 50) {

@@ -1,5 +1,6 @@
 // recparse.h -- the staged-bytes view and the integer grammar every parser of the record text shares
-// (decomp.hip: run lines, record line, fetch; locate.hip: the token list of the locate index).
+// (decomp.hip: run lines, record line, fetch; locate.hip: the token list of the locate index;
+// segments.hip: the segment starts of the record blocks under a region).
 #pragma once
 
 #include "common.h"

@@ -35,6 +35,7 @@
 #include "decomp.h"
 #include "internal.h"
 #include "locate.h"
+#include "segments.h"
 
 static thread_local char g_hip_err[512];
 
@@ -303,6 +304,7 @@ struct sccg_cohort {
     sccg_ctx* ctx = nullptr;
     std::vector<int64_t> length;   // per sample
     std::vector<uint8_t> coords;   // per sample: its reader has reference coordinates
+    std::vector<int64_t> rec_blocks;   // per sample: the 64-byte blocks of its record line (the segments call's grid bound)
     void* d_tab = nullptr;         // DcCohortEntry per sample
     FetchStage stage;
     // locate: per sample, |R| when its reader had enabled locating at create (else -1), and the device
@@ -2065,6 +2067,143 @@ int locate_run(sccg_ctx* ctx, FetchStage& st, const Loci& loci, size_t n, LcLoca
     return SCCG_OK;
 }
 
+// -------------------------------------------------------------------------------------------
+// segments (sccg_*_segments): a region's alignment to the reference, run-length coded
+// -------------------------------------------------------------------------------------------
+int segments_align_check(sccg_ctx* ctx, const void* d_off, const void* d_seg) {
+    if ((uintptr_t)d_off % 8) return ctx->fail(SCCG_E_INVALID, "d_off is not aligned to the 8-byte element");
+    if ((uintptr_t)d_seg % 8) return ctx->fail(SCCG_E_INVALID, "d_seg is not aligned to the 8-byte element");
+    return SCCG_OK;
+}
+
+// a reader's regions: reference coordinates, then every region (as the origin fetch checks them)
+int segments_check(sccg_reader* rd, const sccg_region* regions, size_t n, int64_t* bound) {
+    const sccg_fetch_format origin{SCCG_ENC_ORIGIN, SCCG_DT_I32, 0, 0};
+    int64_t F = 0;
+    int rc = fetch_coords_check(rd, &origin);
+    if (!rc) rc = fetch_check(rd, regions, n, &F);
+    *bound = (int64_t)n * ((rd->src.nrec + 63) / 64 + 1);
+    return rc;
+}
+
+// a cohort's: one pass, the first offender in list order decides; forward strand only
+int cohort_segments_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n, int64_t* bound) {
+    sccg_ctx* ctx = co->ctx;
+    if (!regions && n) return ctx->fail(SCCG_E_INVALID, "null region list");
+    const int64_t ns = (int64_t)co->length.size();
+    int64_t items = 0;
+    for (size_t i = 0; i < n; i++) {
+        const sccg_cohort_region& r = regions[i];
+        if (r.flags) return ctx->fail(SCCG_E_INVALID, "region %zu has flag bits set (flags %u): segments are forward only", i, r.flags);
+        if (r.sample < 0 || r.sample >= ns)
+            return ctx->fail(SCCG_E_INVALID, "region %zu names sample %d, outside [0, %lld)", i, (int)r.sample, (long long)ns);
+        const int64_t len = co->length[(size_t)r.sample];
+        if (r.begin < 0 || r.end < r.begin || r.end > len)
+            return ctx->fail(SCCG_E_INVALID, "region %zu [%lld, %lld) is outside sample %d's sequence [0, %lld)", i,
+                             (long long)r.begin, (long long)r.end, (int)r.sample, (long long)len);
+        if (!co->coords[(size_t)r.sample])
+            return ctx->fail(SCCG_E_UNSUPPORTED, "region %zu reads sample %d, whose reader has no reference coordinates "
+                             "(open it through a sccg_reference with SCCG_REF_COORDS)", i, (int)r.sample);
+        items += co->rec_blocks[(size_t)r.sample] + 1;
+    }
+    *bound = items;
+    return SCCG_OK;
+}
+
+// Regions validated, n > 0.  ONE pinned image -- the n begins, the n ends, then, for a cohort, the samples
+// as int32 -- in one copy, the scratch behind it in the same allocation.  d_seg given: the device forms,
+// all six launches queued back to back (the write is clipped to cap on the device) and the one host read
+// of the total behind them, which is the call's synchronise and its capacity check; d_seg NULL with h_out
+// NULL: the size query, four launches and the read.  h_out: the host forms -- four launches, the read (it
+// sizes the buffers), two launches, one sync -- through the stage's own device output and a malloc'd buffer.
+template <typename Regions>
+int segments_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, SgCall c, int64_t bound, void* d_off, void* d_seg,
+                 size_t cap, size_t* n_seg, int64_t* h_off, sccg_buf* h_out, hipStream_t s) {
+    constexpr bool samples = Regions::samples;
+    HIPTRY(hipSetDevice(ctx->device));
+    const size_t n4 = (n * sizeof(int32_t) + 7) & ~(size_t)7;
+    const size_t img = 2 * n * sizeof(int64_t) + (samples ? n4 : 0);
+    const size_t bytes = img + (size_t)sg_scratch_words((int64_t)n) * sizeof(int64_t);
+    size_t rcap = 0;
+    hipError_t e = st.reserve_regions(bytes, &rcap);
+    if (e != hipSuccess) return reader_alloc_fail(ctx, e, rcap);
+    int64_t* h = st.h_reg;
+    int32_t* hs = reinterpret_cast<int32_t*>(h + 2 * n);
+    for (size_t i = 0; i < n; i++) {
+        const FetchItem r = regions(i);
+        h[i] = r.begin;
+        h[n + i] = r.end;
+        if (samples) hs[i] = r.sample;
+    }
+    int64_t* d = reinterpret_cast<int64_t*>(st.d_reg);
+    HIPTRY(hipMemcpyAsync(d, h, img, hipMemcpyHostToDevice, s));
+    c.d_beg = d;
+    c.d_end = d + n;
+    c.d_samp = samples ? reinterpret_cast<const int32_t*>(d + 2 * n) : nullptr;
+    c.nreg = (int64_t)n;
+    c.bound_items = bound;
+    c.d_scratch = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(d) + img);
+    TRY(sg_count(c, s));
+    if (!h_out && d_seg)   // (no host wait before it: slots beyond cap are not written, and such a call fails below)
+        TRY(sg_write(c, (int64_t)(cap < (size_t)INT64_MAX / 64 ? cap : (size_t)INT64_MAX / 64), reinterpret_cast<int64_t*>(d_off),
+                     reinterpret_cast<sccg_segment*>(d_seg), s));
+    int64_t total = 0;
+    {
+        const RbItem it{sg_total_slot(c), &total, (int)sizeof total};
+        TRY(dev_readback(&it, 1, s));   // (behind everything queued on s: the call's synchronise)
+    }
+    if (total < 0) return ctx->fail(SCCG_E_INTERNAL, "segments: a count of %lld", (long long)total);
+    if (n_seg) *n_seg = (size_t)total;
+    if (!h_out) {
+        if (d_seg && (size_t)total > cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu segments", (size_t)total);
+        return SCCG_OK;
+    }
+    const size_t seg_bytes = (size_t)total * sizeof(sccg_segment), off_bytes = (n + 1) * sizeof(int64_t);
+    char* hb = (char*)malloc(seg_bytes + 1);
+    if (!hb) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
+    const auto fill = [&]() -> int {
+        size_t ocap = 0;
+        e = st.reserve_out(seg_bytes + off_bytes, &ocap);
+        if (e != hipSuccess) return reader_alloc_fail(ctx, e, ocap);
+        int64_t* o = reinterpret_cast<int64_t*>(st.d_out);   // the offsets, then the segments
+        TRY(sg_write(c, total, o, reinterpret_cast<sccg_segment*>(o + n + 1), s));
+        HIPTRY(hipStreamSynchronize(s));
+        if (seg_bytes) HIPTRY(hipMemcpy(hb, o + n + 1, seg_bytes, hipMemcpyDeviceToHost));
+        if (h_off) HIPTRY(hipMemcpy(h_off, o, off_bytes, hipMemcpyDeviceToHost));
+        return SCCG_OK;
+    };
+    const int rc = fill();
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        free(hb);
+        return rc;
+    }
+    hb[seg_bytes] = 0;
+    h_out->data = hb;
+    h_out->len = seg_bytes;
+    return SCCG_OK;
+}
+
+// n == 0: no segments, off[0] = 0
+int segments_none(sccg_ctx* ctx, void* d_off, size_t* n_seg, int64_t* h_off, sccg_buf* h_out, hipStream_t s) {
+    if (n_seg) *n_seg = 0;
+    if (h_out) {
+        char* hb = (char*)malloc(1);
+        if (!hb) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
+        hb[0] = 0;
+        h_out->data = hb;
+        h_out->len = 0;
+        if (h_off) h_off[0] = 0;
+        return SCCG_OK;
+    }
+    if (d_off) {
+        HIPTRY(hipSetDevice(ctx->device));
+        HIPTRY(hipMemsetAsync(d_off, 0, sizeof(int64_t), s));
+        HIPTRY(hipStreamSynchronize(s));
+    }
+    return SCCG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2341,6 +2480,7 @@ int sccg_cohort_create(sccg_reader* const* readers, size_t n_samples, sccg_cohor
         tab[i] = DcCohortEntry{S, S.nr.n, S.lr.n, S.nr.total};
         co->length[i] = readers[i]->length;
         co->coords[i] = readers[i]->has_coords ? 1 : 0;
+        co->rec_blocks.push_back((S.nrec + 63) / 64);
     }
     const size_t bytes = n_samples * sizeof(DcCohortEntry);
     hipError_t e = hipMalloc(&co->d_tab, bytes);
@@ -2470,6 +2610,61 @@ int sccg_cohort_locate(sccg_cohort* cohort, const sccg_cohort_locus* loci, size_
     LcLocate c{};
     c.d_tab = reinterpret_cast<const LcSrc*>(cohort->d_ltab);
     return locate_run(ctx, cohort->stage, CohortLoci{loci}, n, c, nullptr, nullptr, pos, copies, ctx->stream);
+}
+
+int sccg_reader_segments_device(sccg_reader* reader, const sccg_region* regions, size_t n, void* d_off, void* d_seg, size_t cap,
+                                size_t* n_seg, void* stream) {
+    if (!reader || !n_seg) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    int64_t bound = 0;
+    int rc = segments_align_check(ctx, d_off, d_seg);
+    if (!rc) rc = segments_check(reader, regions, n, &bound);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_seg ? d_off : nullptr, n_seg, nullptr, nullptr, s);
+    SgCall c{};
+    c.src = &reader->src;
+    return segments_run(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, bound, d_off, d_seg, cap, n_seg, nullptr, nullptr, s);
+}
+
+int sccg_reader_segments(sccg_reader* reader, const sccg_region* regions, size_t n, int64_t* off, sccg_buf* out) {
+    if (!reader || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    int64_t bound = 0;
+    const int rc = segments_check(reader, regions, n, &bound);
+    if (rc) return rc;   // (nothing written: *out and off are the caller's as they were)
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    SgCall c{};
+    c.src = &reader->src;
+    return segments_run(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, bound, nullptr, nullptr, 0, nullptr, off, out,
+                        ctx->stream);
+}
+
+int sccg_cohort_segments_device(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, void* d_off, void* d_seg, size_t cap,
+                                size_t* n_seg, void* stream) {
+    if (!cohort || !n_seg) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    int64_t bound = 0;
+    int rc = segments_align_check(ctx, d_off, d_seg);
+    if (!rc) rc = cohort_segments_check(cohort, regions, n, &bound);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_seg ? d_off : nullptr, n_seg, nullptr, nullptr, s);
+    SgCall c{};
+    c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
+    return segments_run(ctx, cohort->stage, CohortRegions{regions}, n, c, bound, d_off, d_seg, cap, n_seg, nullptr, nullptr, s);
+}
+
+int sccg_cohort_segments(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, int64_t* off, sccg_buf* out) {
+    if (!cohort || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    int64_t bound = 0;
+    const int rc = cohort_segments_check(cohort, regions, n, &bound);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    SgCall c{};
+    c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
+    return segments_run(ctx, cohort->stage, CohortRegions{regions}, n, c, bound, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
 }
 
 // match_sequences seam (compression.cpp:36): local segments or the windowed global walk

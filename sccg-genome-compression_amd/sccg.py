@@ -203,6 +203,12 @@ def load_library():
         lib.sccg_reader_locate_device.argtypes = [vp, i64p, sz, vp, vp, vp]
         lib.sccg_cohort_locate.argtypes = [vp, ctypes.POINTER(CohortLocus), sz, i64p, i32p]
         lib.sccg_cohort_locate_device.argtypes = [vp, ctypes.POINTER(CohortLocus), sz, vp, vp, vp]
+    if hasattr(lib, "sccg_reader_segments"):   # (absent from builds older than segments: A/B runs)
+        i64p = ctypes.POINTER(i64)
+        lib.sccg_reader_segments.argtypes = [vp, ctypes.POINTER(Region), sz, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_reader_segments_device.argtypes = [vp, ctypes.POINTER(Region), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
+        lib.sccg_cohort_segments.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_cohort_segments_device.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -687,6 +693,19 @@ class Reader:
             self.ctx._err(rc)
         return pos, copies
 
+    def segments(self, regions):
+        """The regions' alignment to the reference, run-length coded (sccg_reader_segments): (off int64 [n + 1],
+        seg int64 [m, 3]) -- region i's segments are seg[off[i]:off[i + 1]], rows (pos, len, ref): `len` bases
+        from sequence position `pos` copied from reference positions ref, ref + 1, ... (ref >= 0), all
+        literals (ref -1) or all of a target N run (ref -2); maximal, tiling the region.  Needs has_coords."""
+        regions, arr = self._regions(regions)
+        return _segments_host(self.ctx, self.lib.sccg_reader_segments, self.ptr, arr, len(regions))
+
+    def segments_tensor(self, regions, stream=None):
+        """segments() into torch tensors on the context's device."""
+        regions, arr = self._regions(regions)
+        return _segments_tensor(self.ctx, self.lib.sccg_reader_segments_device, self.ptr, arr, len(regions), stream)
+
     def locate_tensor(self, ref_positions, stream=None):
         """locate() into torch tensors on the context's device: (pos int64 [n], copies int32 [n])."""
         import numpy as np
@@ -700,6 +719,35 @@ class Reader:
         if rc:
             self.ctx._err(rc)
         return pos, copies
+
+
+def _segments_host(ctx, call, ptr, arr, n):
+    """(off int64 [n + 1], seg int64 [m, 3]) of a host segments call (sccg_*_segments)."""
+    import numpy as np
+    off = np.zeros(n + 1, dtype=np.int64)
+    buf = Buf()
+    rc = call(ptr, arr, n, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(buf))
+    if rc:
+        ctx._err(rc)
+    return off, np.frombuffer(ctx._take(buf), dtype="<i8").reshape(-1, 3).copy()
+
+
+def _segments_tensor(ctx, call, ptr, arr, n, stream):
+    """The same pair as device tensors (sccg_*_segments_device): one call to size, one into exactly-sized tensors."""
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    s = torch.cuda.current_stream(dev) if stream is None else stream
+    m = ctypes.c_size_t()
+    rc = call(ptr, arr, n, None, None, 0, ctypes.byref(m), s.cuda_stream or None)
+    if rc:
+        ctx._err(rc)
+    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    seg = torch.empty((m.value, 3), dtype=torch.int64, device=dev)
+    if m.value:
+        rc = call(ptr, arr, n, off.data_ptr(), seg.data_ptr(), m.value, ctypes.byref(m), s.cuda_stream or None)
+        if rc:
+            ctx._err(rc)
+    return off, seg
 
 
 class Cohort:
@@ -797,6 +845,16 @@ class Cohort:
         if len(lens) == 1 and items:
             out = out.view(len(items), lens.pop(), *shape[1:])
         return out
+
+    def segments(self, items):
+        """Reader.segments over the cohort (sccg_cohort_segments): items (sample, begin, end), forward only."""
+        rows, arr = self._items(items)
+        return _segments_host(self.ctx, self.lib.sccg_cohort_segments, self.ptr, arr, len(rows))
+
+    def segments_tensor(self, items, stream=None):
+        """segments() into torch tensors on the context's device."""
+        rows, arr = self._items(items)
+        return _segments_tensor(self.ctx, self.lib.sccg_cohort_segments_device, self.ptr, arr, len(rows), stream)
 
     @staticmethod
     def _loci(items):

@@ -26,7 +26,11 @@ call by call; and sccg_reference_open_device with and without SCCG_REF_COORDS.  
 that last section alone.  --only-locate runs the locate leg alone: sccg_reader_enable_locate (host ms, index
 bytes), sccg_reader_locate_device and sccg_cohort_locate_device for 1 / 1,000 / 100,000 random reference
 positions (every located base checked against the reference), the 1000 x 1 kb index and origin fetches
-of the same run, and Cohort.fetch_tensor_at beside the fetch_tensor it wraps.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
+of the same run, and Cohort.fetch_tensor_at beside the fetch_tensor it wraps.  --only-segments runs the
+segments leg alone: sccg_reader_segments_device / sccg_cohort_segments_device at 1 x 1 Mb, 1000 x 1 kb,
+1 x 10 Mb and the whole sequence beside what they replace -- the origin fetch of the same regions plus a run-length coding of its
+output on the device in PyTorch -- interleaved call by call, with the segment counts and the bytes either
+writes; the segments are checked by expanding them back to the origin fetch's output.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
 must name the reference base the target's base is, -2 an N).  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
@@ -353,6 +357,98 @@ def locate_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec,
     return out
 
 
+def segments_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, rec_len, S=8):
+    """The segments call beside the origin fetch + a run-length coding in PyTorch, reader and S-sample cohort."""
+    s = stream.cuda_stream
+    out = {"samples": S, "same_record": True, "shapes": {}}
+    ref = ctx.open_reference_device(d_ref.data_ptr(), ref_len, stream=s, coords=True)
+    readers = [ref.open_reader_device(d_rec.data_ptr(), rec_len, s) for _ in range(S)]
+    rd, co = readers[0], sccg.Cohort(readers)
+    L = rd.length
+    rng = random.Random(7)
+    fmt = sccg.FetchFormat(sccg.ENCODINGS["origin"], sccg.DTYPES["i32"], 0, 0)
+    # (the whole sequence is beyond the three shapes asked for: where the one-launch origin fetch's bytes outweigh
+    # the segments call's six launches)
+    for name, (n, ln) in {"1x1Mb": (1, 1_000_000), "1000x1kb": (1000, 1000), "1x10Mb": (1, 10_000_000), "1xwhole": (1, L)}.items():
+        begins = [rng.randrange(L - ln + 1) for _ in range(n)]
+        samp = [k % S for k in range(n)]
+        rng.shuffle(samp)
+        F = n * ln
+        flat = (sccg.Region * n)(*[(b, b + ln) for b in begins])
+        items = (sccg.CohortRegion * n)(*[(b, b + ln, sm, 0) for b, sm in zip(begins, samp)])
+        d_org = torch.empty(F, dtype=torch.int32, device=dev)
+        d_beg = torch.tensor(begins, dtype=torch.int64, device=dev)
+        got = ctypes.c_size_t()
+        for who in ("reader", "cohort"):
+            seg_call = lib.sccg_reader_segments_device if who == "reader" else lib.sccg_cohort_segments_device
+            h, regs = (rd.ptr, flat) if who == "reader" else (co.ptr, items)
+            assert seg_call(h, regs, n, None, None, 0, ctypes.byref(got), s) == 0   # the size query, outside the timing
+            m = got.value
+            d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            d_seg = torch.empty((m, 3), dtype=torch.int64, device=dev)
+            rle = [None]
+
+            def segments():
+                assert seg_call(h, regs, n, d_off.data_ptr(), d_seg.data_ptr(), m, ctypes.byref(got), s) == 0 and got.value == m
+
+            def size_query():
+                assert seg_call(h, regs, n, None, None, 0, ctypes.byref(got), s) == 0 and got.value == m
+
+            def origin():
+                if who == "reader":
+                    rc = lib.sccg_reader_fetch_encoded_device(h, regs, n, None, ctypes.byref(fmt), d_org.data_ptr(), 4 * F, ctypes.byref(got), s)
+                else:
+                    rc = lib.sccg_cohort_fetch_device(h, regs, n, ctypes.byref(fmt), d_org.data_ptr(), 4 * F, ctypes.byref(got), s)
+                assert rc == 0 and got.value == 4 * F, (rc, got.value)
+
+            def origin_rle():
+                origin()
+                o = d_org.view(n, ln)
+                start = torch.ones((n, ln), dtype=torch.bool, device=dev)
+                start[:, 1:] = ~torch.where(o[:, :-1] >= 0, o[:, 1:] == o[:, :-1] + 1, o[:, 1:] == o[:, :-1])
+                at = torch.nonzero(start.view(-1)).view(-1)   # (a host wait for the count, as the segments call's one read)
+                end = torch.cat([at[1:], torch.tensor([F], dtype=torch.int64, device=dev)])
+                row = torch.div(at, ln, rounding_mode="floor")
+                rle[0] = torch.stack([d_beg[row] + (at - row * ln), end - at, d_org[at].long()], dim=1)
+
+            calls = {"segments": segments, "size_query": size_query, "origin_fetch": origin, "origin_fetch_plus_rle": origin_rle}
+            ev = {k: [] for k in calls}
+            for i in range(a.warmup + a.calls):   # interleaved: every leg once per round
+                for k, call in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    e0.record(stream)
+                    call()
+                    e1.record(stream)
+                    stream.synchronize()
+                    if i >= a.warmup:
+                        ev[k].append(e0.elapsed_time(e1))
+            ctx.profile(True, families=["fetch"])
+            for _ in range(a.calls):
+                segments()
+            kern = ctx.profile_get().get("fetch", (0.0, 0))
+            ctx.profile(False)
+            ln_ = d_seg[:, 1]
+            k_in = torch.arange(F, device=dev) - torch.repeat_interleave(torch.cumsum(ln_, 0) - ln_, ln_)
+            r_in = torch.repeat_interleave(d_seg[:, 2], ln_)
+            exact = bool(int(ln_.sum()) == F and torch.equal(torch.where(r_in >= 0, r_in + k_in, r_in), d_org.long())
+                         and torch.equal(rle[0], d_seg) and int(d_off[-1]) == m)
+            med = {k: statistics.median(v) for k, v in ev.items()}
+            out["shapes"][f"{name}/{who}"] = {
+                "bases": F, "segments": m, "segment_bytes": 24 * m + 8 * (n + 1), "origin_bytes": 4 * F,
+                "event_ms": {k: spread(v) for k, v in ev.items()}, "kernels_ms_per_call": round(kern[0] / a.calls, 4),
+                "launches_per_call": kern[1] / a.calls, "origin_over_segments": round(med["origin_fetch"] / med["segments"], 2),
+                "origin_rle_over_segments": round(med["origin_fetch_plus_rle"] / med["segments"], 2), "exact": exact}
+            del d_off, d_seg, k_in, r_in
+            rle[0] = None
+        del d_org
+    co.close()
+    for r in readers:
+        r.close()
+    ref.close()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", default="hg")
@@ -363,6 +459,7 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only-origin", action="store_true", help="the origin section alone")
     ap.add_argument("--only-locate", action="store_true", help="the locate section alone")
+    ap.add_argument("--only-segments", action="store_true", help="the segments section alone")
     a = ap.parse_args()
     import torch
     import sccg
@@ -399,6 +496,14 @@ def main() -> None:
     code = [4] * 256
     for k, ch in enumerate(b"ACGT"):
         code[ch] = code[ch + 32] = k
+    if a.only_segments:
+        out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
+               "segments": segments_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h))}
+        ctx.close()
+        print(json.dumps(out))
+        if not all(v["exact"] for v in out["segments"]["shapes"].values()):
+            raise SystemExit("bench_fetch: segments section: the segments do not expand to the origin fetch")
+        return
     if a.only_locate:
         loc = locate_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth, rfa)
         loc["record_line_tokens"] = rec_h.rstrip(b"\n").rpartition(b"\n")[2].count(b"(")   # (zero-length ones included)
