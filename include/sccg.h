@@ -37,6 +37,8 @@
  * sccg_reader_segments / _device,     a region's alignment to the reference, run-length coded: the gapless
  *   sccg_cohort_segments / _device      blocks, literals and N runs the origin fetch spells out per base
  *                                       (no counterpart)
+ * sccg_reader_lift / _device,         intervals of the reference onto a sample, run-length coded: what
+ *   sccg_cohort_lift / _device          locate spells out per reference base (no counterpart)
  *
  * Conventions: status ints (0 = OK); the library never calls exit(); host buffers it returns are
  * malloc'ed and released with sccg_buf_free.  One context per GPU; a context is not re-entrant;
@@ -504,6 +506,60 @@ int sccg_reader_segments_device(sccg_reader* reader, const sccg_region* regions 
 int sccg_cohort_segments(sccg_cohort* cohort, const sccg_cohort_region* regions, size_t n, int64_t* off, sccg_buf* out);
 int sccg_cohort_segments_device(sccg_cohort* cohort, const sccg_cohort_region* regions /*host*/, size_t n, void* d_off, void* d_seg,
                                 size_t cap, size_t* n_seg, void* stream);
+
+/* Lift: intervals of the reference onto a sample, run-length coded -- where an exon, an enhancer, a BED
+ * line of the reference lies in the sample, and which parts of it are missing.  What locate says with 12
+ * bytes per reference base, this says with 24 bytes per block, and its work is in proportion to the token
+ * boundaries and runs under the intervals, not to their bases: segments, mirrored onto the reference axis.
+ *
+ * For a reader that has enabled locating (sccg_reader_enable_locate) let pos(r) be what sccg_reader_locate
+ * returns for reference position r, 0 <= r < |R|.  A block of interval [begin, end) is a maximal interval
+ * [a, b) inside it such that for every r in [a, b - 1) pos(r) >= 0 and pos(r + 1) == pos(r) + 1, or both
+ * are -1, or both are -2; it is reported as {ref = a, len = b - a, pos = pos(a)}.  The blocks of an
+ * interval tile it exactly, in ascending ref; an empty interval has none; they are clipped to the interval,
+ * so pos belongs to the first reference base inside it; no two neighbours could merge.  The definition
+ * speaks of bases, never of tokens:
+ *   - a block goes on where the same first covering token goes on (later tokens over it, nested or
+ *     overlapping, change `copies`, not pos), and where another token continues it on both axes: "(100,30)
+ *     (130,20)" back to back is one block, zero-length tokens between them change nothing;
+ *   - it is cut where a target N run was put into a token (pos jumps there), and where the first covering
+ *     token ends and a different one takes over;
+ *   - it is cut on both sides of every erased run of 'N' in R: each such run, or its part inside the
+ *     interval, is one -2 block.  A record whose N line is "," has no -2 blocks;
+ *   - positions before the first token boundary, behind the last one or in an uncovered gap give -1 blocks;
+ *     a record without any token gives -1 and -2 blocks only;
+ *   - with duplicated reference bases (copies > 1) the lift follows locate: the first covering token in
+ *     record order wins.  `copies` is not reported -- it is not constant over a block; locate gives it per
+ *     position.
+ *
+ * The layout is sccg_*_segments*'s: the blocks of interval i are out[off[i], off[i + 1]), off[0] == 0,
+ * off[n] the total; intervals may be empty, repeat, overlap and come in any order of positions and samples;
+ * n == 0 is SCCG_OK with no blocks (off[0] = 0).  The host forms return the sccg_lift_block array in *out
+ * (out->len bytes; sccg_buf_free) and, when `off` is given, the n + 1 offsets.  The _device forms write
+ * int64 offsets to d_off (may be NULL) and blocks to d_blk, device memory, on `stream` (a hipStream_t; NULL =
+ * the context's own): d_blk == NULL is a size query that only sets *n_blk; with cap (in blocks) too small
+ * they return SCCG_E_NOMEM, *n_blk the number needed, the buffers' contents unspecified.  Both forms
+ * synchronise before returning.
+ *
+ * Costs: the locate index is read exactly as it is and gets no new array, so sccg_reader_device_bytes does
+ * not change; the scratch lives in the staging the call grows, as for segments.  Six kernel launches, one
+ * copy of the interval list and one host read (the total) per call, whatever n, the interval sizes and the
+ * samples touched are (four launches for a size query).
+ *
+ * SCCG_E_INVALID, nothing written, sccg_last_error naming the first offender ("interval k"): a NULL reader /
+ * cohort / out / n_blk; a NULL list with n > 0; d_off or d_blk not 8-byte aligned; an interval outside 0 <=
+ * begin <= end <= |R| of its own sample; in a cohort a sample outside [0, n_samples) or any flag bit set.
+ * SCCG_E_UNSUPPORTED, the size query included: a reader that has not enabled locating; in a cohort an
+ * interval whose sample had not enabled locating before sccg_cohort_create.  The intervals are checked in
+ * one pass and the first offender in list order decides the status. */
+typedef struct { int64_t ref, len, pos; } sccg_lift_block;   /* pos >= 0, -1 no copy, -2 erased N of the reference */
+int sccg_reader_lift(sccg_reader* reader, const sccg_region* intervals /*of R, 0-based half-open*/, size_t n,
+                     int64_t* off /*host, n + 1; may be NULL*/, sccg_buf* out /*sccg_lift_block[]*/);
+int sccg_reader_lift_device(sccg_reader* reader, const sccg_region* intervals /*host*/, size_t n,
+                            void* d_off /*int64[n + 1] or NULL*/, void* d_blk, size_t cap /*blocks*/, size_t* n_blk, void* stream);
+int sccg_cohort_lift(sccg_cohort* cohort, const sccg_cohort_region* intervals, size_t n, int64_t* off, sccg_buf* out);
+int sccg_cohort_lift_device(sccg_cohort* cohort, const sccg_cohort_region* intervals /*host*/, size_t n, void* d_off, void* d_blk,
+                            size_t cap, size_t* n_blk, void* stream);
 
 void sccg_buf_free(sccg_buf* b);
 

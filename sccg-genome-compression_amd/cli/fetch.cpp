@@ -13,6 +13,8 @@
 // and inclusive -- `tbegin tend rbegin rend` for bases copied from consecutively ascending reference
 // positions, `tbegin tend *` for literals of the record line, `tbegin tend N` for bases of the target's
 // N runs.  --origin together with -i is a usage error.
+// `fetch --locate ...` and `fetch --lift ...` (first argument only) ask the other way round, from the
+// reference to the sequence: locate_main and lift_main below.
 #include "cli_common.h"
 
 #include <cstring>
@@ -33,7 +35,7 @@ static bool parse_pos(const std::string& s, int64_t* v) {
 // tab-separated, 1-based; pos is `-` when no token copies the position and `N` inside an erased N run
 static int locate_main(int argc, char* argv[]) {
     const bool mixed = argc > 2 && (std::string(argv[2]) == "-i" || std::string(argv[2]) == "--reverse-complement" ||
-                                    std::string(argv[2]) == "--origin");
+                                    std::string(argv[2]) == "--origin" || std::string(argv[2]) == "--lift");
     if (argc < 5 || mixed) {
         std::cerr << "Usage: " << argv[0] << " --locate <record_file> <reference_file> <refpos>...\n"
                   << "  refpos: a 1-based position of the reference sequence; prints refpos, the first 1-based sequence\n"
@@ -91,13 +93,93 @@ static int locate_main(int argc, char* argv[]) {
     return 0;
 }
 
+// `fetch --lift <record_file> <reference_file> <refregion>...`: per region of the reference sequence
+// (`begin-end`, 1-based inclusive, or a bare `pos`) a line `>begin-end`, then one tab-separated line per
+// block (sccg_reader_lift), everything 1-based and inclusive: `rbegin rend tbegin tend` for reference bases
+// that lie at consecutively ascending sequence positions, `rbegin rend -` where no token copies them,
+// `rbegin rend N` for an erased N run of the reference
+static int lift_main(int argc, char* argv[]) {
+    const std::string a2 = argc > 2 ? argv[2] : "";
+    const bool mixed = a2 == "-i" || a2 == "--reverse-complement" || a2 == "--origin" || a2 == "--locate";
+    if (argc < 5 || mixed) {
+        std::cerr << "Usage: " << argv[0] << " --lift <record_file> <reference_file> <refregion>...\n"
+                  << "  refregion: begin-end (1-based, inclusive) or pos, of the reference sequence; prints >begin-end, then\n"
+                  << "  one line per block: rbegin rend tbegin tend (where the bases lie in the sequence) | rbegin rend -\n"
+                  << "  (no copy) | rbegin rend N (an erased reference N run)\n"
+                  << "  --lift is the first argument only, not with -i, --origin or --locate\n";
+        return 1;
+    }
+    std::vector<sccg_region> iv;
+    for (int i = 4; i < argc; i++) {
+        const std::string a = argv[i];
+        const size_t dash = a.find('-');
+        int64_t b = 0, e = 0;
+        const bool ok = dash == std::string::npos ? parse_pos(a, &b) && (e = b, true)
+                                                  : parse_pos(a.substr(0, dash), &b) && parse_pos(a.substr(dash + 1), &e);
+        if (!ok || b < 1 || e < b) {
+            std::cerr << "Error: malformed reference region '" << a << "' (begin-end, 1-based, inclusive, begin <= end)\n";
+            return 1;
+        }
+        iv.push_back(sccg_region{b - 1, e});
+    }
+    std::string ref, rec;
+    if (!slurp(argv[3], ref)) {
+        std::cerr << "Greska pri otvaranju reference: " << argv[3] << "\n";
+        return 1;
+    }
+    if (!slurp(argv[2], rec)) {
+        std::cerr << "Greska pri otvaranju datoteke: " << argv[2] << "\n";
+        return 1;
+    }
+    sccg_ctx* ctx = nullptr;
+    int rc = sccg_ctx_create(cli_device(), &ctx);
+    if (rc) {
+        std::cerr << "Error: no usable GPU (sccg_ctx_create rc=" << rc << ")\n";
+        return 1;
+    }
+    sccg_reference* rf = nullptr;
+    sccg_reader* rd = nullptr;
+    rc = sccg_reference_open(ctx, ref.data(), ref.size(), SCCG_REF_COORDS, &rf);
+    if (!rc) rc = sccg_reader_open_shared(rf, rec.data(), rec.size(), &rd);
+    sccg_reference_close(rf);
+    if (!rc) rc = sccg_reader_enable_locate(rd);
+    sccg_buf blk{};
+    std::vector<int64_t> off(iv.size() + 1);
+    if (!rc) rc = sccg_reader_lift(rd, iv.data(), iv.size(), off.data(), &blk);
+    if (rc) {
+        std::cerr << "Error lifting: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_reader_close(rd);
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    std::string out;
+    for (size_t i = 0; i < iv.size(); i++) {
+        out += ">" + std::to_string(iv[i].begin + 1) + "-" + std::to_string(iv[i].end) + "\n";
+        for (int64_t k = off[i]; k < off[i + 1]; k++) {
+            sccg_lift_block g;
+            memcpy(&g, blk.data + (size_t)k * sizeof g, sizeof g);
+            out += std::to_string(g.ref + 1) + "\t" + std::to_string(g.ref + g.len) + "\t";
+            if (g.pos >= 0) out += std::to_string(g.pos + 1) + "\t" + std::to_string(g.pos + g.len);
+            else out += g.pos == SCCG_LOCATE_REF_N ? "N" : "-";
+            out += '\n';
+        }
+    }
+    std::cout << out;
+    sccg_buf_free(&blk);
+    sccg_reader_close(rd);
+    sccg_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
+    if (argc > 1 && std::string(argv[1]) == "--lift") return lift_main(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "--locate") return locate_main(argc, argv);
     const bool rc_flag = argc > 1 && (std::string(argv[1]) == "-i" || std::string(argv[1]) == "--reverse-complement");
     const bool origin = argc > 1 && std::string(argv[1]) == "--origin";
     const int a0 = rc_flag || origin ? 2 : 1;   // the first file argument
     const bool both = argc > 2 && ((origin && (std::string(argv[2]) == "-i" || std::string(argv[2]) == "--reverse-complement")) ||
-                                   (rc_flag && std::string(argv[2]) == "--origin"));
+                                   (rc_flag && std::string(argv[2]) == "--origin") ||
+                                   ((origin || rc_flag) && std::string(argv[2]) == "--lift"));
     if (argc < a0 + 3 || both) {
         std::cerr << "Usage: " << argv[0] << " [-i | --origin] <record_file> <reference_file> <region>...\n"
                   << "  region: begin-end (1-based, inclusive) or pos\n"

@@ -36,6 +36,7 @@
 #include "internal.h"
 #include "locate.h"
 #include "segments.h"
+#include "lift.h"
 
 static thread_local char g_hip_err[512];
 
@@ -311,6 +312,7 @@ struct sccg_cohort {
     // table of their LcSrc (null when none had)
     std::vector<int64_t> ref_bases;
     void* d_ltab = nullptr;
+    int64_t loc_leaves = 0;        // the elementary intervals of all their indexes (the lift call's grid bound)
 };
 
 #define TRY(expr)                                  \
@@ -2070,9 +2072,9 @@ int locate_run(sccg_ctx* ctx, FetchStage& st, const Loci& loci, size_t n, LcLoca
 // -------------------------------------------------------------------------------------------
 // segments (sccg_*_segments): a region's alignment to the reference, run-length coded
 // -------------------------------------------------------------------------------------------
-int segments_align_check(sccg_ctx* ctx, const void* d_off, const void* d_seg) {
+int segments_align_check(sccg_ctx* ctx, const void* d_off, const void* d_seg, const char* rows = "d_seg") {
     if ((uintptr_t)d_off % 8) return ctx->fail(SCCG_E_INVALID, "d_off is not aligned to the 8-byte element");
-    if ((uintptr_t)d_seg % 8) return ctx->fail(SCCG_E_INVALID, "d_seg is not aligned to the 8-byte element");
+    if ((uintptr_t)d_seg % 8) return ctx->fail(SCCG_E_INVALID, "%s is not aligned to the 8-byte element", rows);
     return SCCG_OK;
 }
 
@@ -2110,20 +2112,43 @@ int cohort_segments_check(sccg_cohort* co, const sccg_cohort_region* regions, si
     return SCCG_OK;
 }
 
-// Regions validated, n > 0.  ONE pinned image -- the n begins, the n ends, then, for a cohort, the samples
+// The two run-length coded calls share one host path: what it drives, and how it names a row.
+struct SegmentsOps {
+    using Call = SgCall;
+    using Row = sccg_segment;
+    static constexpr const char* call = "segments";
+    static constexpr const char* rows = "segments";
+    static int64_t scratch_words(int64_t n) { return sg_scratch_words(n); }
+    static const int64_t* total_slot(const Call& c) { return sg_total_slot(c); }
+    static int count(const Call& c, hipStream_t s) { return sg_count(c, s); }
+    static int write(const Call& c, int64_t cap, int64_t* d_off, Row* d_rows, hipStream_t s) { return sg_write(c, cap, d_off, d_rows, s); }
+};
+struct LiftOps {
+    using Call = LfCall;
+    using Row = sccg_lift_block;
+    static constexpr const char* call = "lift";
+    static constexpr const char* rows = "blocks";
+    static int64_t scratch_words(int64_t n) { return lf_scratch_words(n); }
+    static const int64_t* total_slot(const Call& c) { return lf_total_slot(c); }
+    static int count(const Call& c, hipStream_t s) { return lf_count(c, s); }
+    static int write(const Call& c, int64_t cap, int64_t* d_off, Row* d_rows, hipStream_t s) { return lf_write(c, cap, d_off, d_rows, s); }
+};
+
+// Regions (a lift's intervals) validated, n > 0.  ONE pinned image -- the n begins, the n ends, then, for a cohort, the samples
 // as int32 -- in one copy, the scratch behind it in the same allocation.  d_seg given: the device forms,
 // all six launches queued back to back (the write is clipped to cap on the device) and the one host read
 // of the total behind them, which is the call's synchronise and its capacity check; d_seg NULL with h_out
 // NULL: the size query, four launches and the read.  h_out: the host forms -- four launches, the read (it
 // sizes the buffers), two launches, one sync -- through the stage's own device output and a malloc'd buffer.
-template <typename Regions>
-int segments_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, SgCall c, int64_t bound, void* d_off, void* d_seg,
-                 size_t cap, size_t* n_seg, int64_t* h_off, sccg_buf* h_out, hipStream_t s) {
+template <typename Ops = SegmentsOps, typename Regions>
+int segments_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, typename Ops::Call c, int64_t bound, void* d_off,
+                 void* d_seg, size_t cap, size_t* n_seg, int64_t* h_off, sccg_buf* h_out, hipStream_t s) {
+    using Row = typename Ops::Row;
     constexpr bool samples = Regions::samples;
     HIPTRY(hipSetDevice(ctx->device));
     const size_t n4 = (n * sizeof(int32_t) + 7) & ~(size_t)7;
     const size_t img = 2 * n * sizeof(int64_t) + (samples ? n4 : 0);
-    const size_t bytes = img + (size_t)sg_scratch_words((int64_t)n) * sizeof(int64_t);
+    const size_t bytes = img + (size_t)Ops::scratch_words((int64_t)n) * sizeof(int64_t);
     size_t rcap = 0;
     hipError_t e = st.reserve_regions(bytes, &rcap);
     if (e != hipSuccess) return reader_alloc_fail(ctx, e, rcap);
@@ -2143,22 +2168,22 @@ int segments_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n
     c.nreg = (int64_t)n;
     c.bound_items = bound;
     c.d_scratch = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(d) + img);
-    TRY(sg_count(c, s));
+    TRY(Ops::count(c, s));
     if (!h_out && d_seg)   // (no host wait before it: slots beyond cap are not written, and such a call fails below)
-        TRY(sg_write(c, (int64_t)(cap < (size_t)INT64_MAX / 64 ? cap : (size_t)INT64_MAX / 64), reinterpret_cast<int64_t*>(d_off),
-                     reinterpret_cast<sccg_segment*>(d_seg), s));
+        TRY(Ops::write(c, (int64_t)(cap < (size_t)INT64_MAX / 64 ? cap : (size_t)INT64_MAX / 64), reinterpret_cast<int64_t*>(d_off),
+                       reinterpret_cast<Row*>(d_seg), s));
     int64_t total = 0;
     {
-        const RbItem it{sg_total_slot(c), &total, (int)sizeof total};
+        const RbItem it{Ops::total_slot(c), &total, (int)sizeof total};
         TRY(dev_readback(&it, 1, s));   // (behind everything queued on s: the call's synchronise)
     }
-    if (total < 0) return ctx->fail(SCCG_E_INTERNAL, "segments: a count of %lld", (long long)total);
+    if (total < 0) return ctx->fail(SCCG_E_INTERNAL, "%s: a count of %lld", Ops::call, (long long)total);
     if (n_seg) *n_seg = (size_t)total;
     if (!h_out) {
-        if (d_seg && (size_t)total > cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu segments", (size_t)total);
+        if (d_seg && (size_t)total > cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu %s", (size_t)total, Ops::rows);
         return SCCG_OK;
     }
-    const size_t seg_bytes = (size_t)total * sizeof(sccg_segment), off_bytes = (n + 1) * sizeof(int64_t);
+    const size_t seg_bytes = (size_t)total * sizeof(Row), off_bytes = (n + 1) * sizeof(int64_t);
     char* hb = (char*)malloc(seg_bytes + 1);
     if (!hb) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
     const auto fill = [&]() -> int {
@@ -2166,7 +2191,7 @@ int segments_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n
         e = st.reserve_out(seg_bytes + off_bytes, &ocap);
         if (e != hipSuccess) return reader_alloc_fail(ctx, e, ocap);
         int64_t* o = reinterpret_cast<int64_t*>(st.d_out);   // the offsets, then the segments
-        TRY(sg_write(c, total, o, reinterpret_cast<sccg_segment*>(o + n + 1), s));
+        TRY(Ops::write(c, total, o, reinterpret_cast<Row*>(o + n + 1), s));
         HIPTRY(hipStreamSynchronize(s));
         if (seg_bytes) HIPTRY(hipMemcpy(hb, o + n + 1, seg_bytes, hipMemcpyDeviceToHost));
         if (h_off) HIPTRY(hipMemcpy(h_off, o, off_bytes, hipMemcpyDeviceToHost));
@@ -2201,6 +2226,45 @@ int segments_none(sccg_ctx* ctx, void* d_off, size_t* n_seg, int64_t* h_off, scc
         HIPTRY(hipMemsetAsync(d_off, 0, sizeof(int64_t), s));
         HIPTRY(hipStreamSynchronize(s));
     }
+    return SCCG_OK;
+}
+
+// -------------------------------------------------------------------------------------------
+// lift (sccg_*_lift): intervals of the reference onto a sample, run-length coded -- segments' host path
+// (segments_run, segments_none, segments_align_check) over lift.h's launchers
+// -------------------------------------------------------------------------------------------
+// a reader's intervals; bound: its elementary intervals + n (the grid of lift.hip's item passes)
+int lift_check(sccg_reader* rd, const sccg_region* iv, size_t n, int64_t* bound) {
+    sccg_ctx* ctx = rd->ctx;
+    if (!rd->can_locate) return ctx->fail(SCCG_E_UNSUPPORTED, "the reader has not enabled locating (sccg_reader_enable_locate)");
+    if (!iv && n) return ctx->fail(SCCG_E_INVALID, "null interval list");
+    for (size_t i = 0; i < n; i++)
+        if (iv[i].begin < 0 || iv[i].end < iv[i].begin || iv[i].end > rd->ref_bases)
+            return ctx->fail(SCCG_E_INVALID, "interval %zu [%lld, %lld) is outside the reference [0, %lld)", i, (long long)iv[i].begin,
+                             (long long)iv[i].end, (long long)rd->ref_bases);
+    *bound = rd->loc.ix.ne + (int64_t)n;
+    return SCCG_OK;
+}
+
+// a cohort's: one pass, the first offender in list order decides
+int cohort_lift_check(sccg_cohort* co, const sccg_cohort_region* iv, size_t n, int64_t* bound) {
+    sccg_ctx* ctx = co->ctx;
+    if (!iv && n) return ctx->fail(SCCG_E_INVALID, "null interval list");
+    const int64_t ns = (int64_t)co->length.size();
+    for (size_t i = 0; i < n; i++) {
+        const sccg_cohort_region& r = iv[i];
+        if (r.flags) return ctx->fail(SCCG_E_INVALID, "interval %zu has flag bits set (flags %u): a lift is forward only", i, r.flags);
+        if (r.sample < 0 || r.sample >= ns)
+            return ctx->fail(SCCG_E_INVALID, "interval %zu names sample %d, outside [0, %lld)", i, (int)r.sample, (long long)ns);
+        const int64_t nR = co->ref_bases[(size_t)r.sample];
+        if (nR < 0)
+            return ctx->fail(SCCG_E_UNSUPPORTED, "interval %zu asks sample %d, whose reader had not enabled locating when the cohort "
+                             "was created (sccg_reader_enable_locate before sccg_cohort_create)", i, (int)r.sample);
+        if (r.begin < 0 || r.end < r.begin || r.end > nR)
+            return ctx->fail(SCCG_E_INVALID, "interval %zu [%lld, %lld) is outside sample %d's reference [0, %lld)", i,
+                             (long long)r.begin, (long long)r.end, (int)r.sample, (long long)nR);
+    }
+    *bound = co->loc_leaves + (int64_t)n;
     return SCCG_OK;
 }
 
@@ -2503,6 +2567,7 @@ int sccg_cohort_create(sccg_reader* const* readers, size_t n_samples, sccg_cohor
         if (!readers[i]->can_locate) continue;
         ltab[i] = readers[i]->loc;
         co->ref_bases[i] = readers[i]->ref_bases;
+        co->loc_leaves += ltab[i].ix.ne;
         any = true;
     }
     if (any) {
@@ -2665,6 +2730,63 @@ int sccg_cohort_segments(sccg_cohort* cohort, const sccg_cohort_region* regions,
     SgCall c{};
     c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
     return segments_run(ctx, cohort->stage, CohortRegions{regions}, n, c, bound, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
+}
+
+int sccg_reader_lift_device(sccg_reader* reader, const sccg_region* intervals, size_t n, void* d_off, void* d_blk, size_t cap,
+                            size_t* n_blk, void* stream) {
+    if (!reader || !n_blk) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    int64_t bound = 0;
+    int rc = segments_align_check(ctx, d_off, d_blk, "d_blk");
+    if (!rc) rc = lift_check(reader, intervals, n, &bound);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_blk ? d_off : nullptr, n_blk, nullptr, nullptr, s);
+    LfCall c{};
+    c.src = &reader->loc;
+    return segments_run<LiftOps>(ctx, reader->stage, ReaderRegions{intervals, nullptr}, n, c, bound, d_off, d_blk, cap, n_blk, nullptr,
+                                 nullptr, s);
+}
+
+int sccg_reader_lift(sccg_reader* reader, const sccg_region* intervals, size_t n, int64_t* off, sccg_buf* out) {
+    if (!reader || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    int64_t bound = 0;
+    const int rc = lift_check(reader, intervals, n, &bound);
+    if (rc) return rc;   // (nothing written: *out and off are the caller's as they were)
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    LfCall c{};
+    c.src = &reader->loc;
+    return segments_run<LiftOps>(ctx, reader->stage, ReaderRegions{intervals, nullptr}, n, c, bound, nullptr, nullptr, 0, nullptr, off,
+                                 out, ctx->stream);
+}
+
+int sccg_cohort_lift_device(sccg_cohort* cohort, const sccg_cohort_region* intervals, size_t n, void* d_off, void* d_blk, size_t cap,
+                            size_t* n_blk, void* stream) {
+    if (!cohort || !n_blk) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    int64_t bound = 0;
+    int rc = segments_align_check(ctx, d_off, d_blk, "d_blk");
+    if (!rc) rc = cohort_lift_check(cohort, intervals, n, &bound);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_blk ? d_off : nullptr, n_blk, nullptr, nullptr, s);
+    LfCall c{};
+    c.d_tab = reinterpret_cast<const LcSrc*>(cohort->d_ltab);
+    return segments_run<LiftOps>(ctx, cohort->stage, CohortRegions{intervals}, n, c, bound, d_off, d_blk, cap, n_blk, nullptr, nullptr, s);
+}
+
+int sccg_cohort_lift(sccg_cohort* cohort, const sccg_cohort_region* intervals, size_t n, int64_t* off, sccg_buf* out) {
+    if (!cohort || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    int64_t bound = 0;
+    const int rc = cohort_lift_check(cohort, intervals, n, &bound);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    LfCall c{};
+    c.d_tab = reinterpret_cast<const LcSrc*>(cohort->d_ltab);
+    return segments_run<LiftOps>(ctx, cohort->stage, CohortRegions{intervals}, n, c, bound, nullptr, nullptr, 0, nullptr, off, out,
+                                 ctx->stream);
 }
 
 // match_sequences seam (compression.cpp:36): local segments or the windowed global walk

@@ -26,3 +26,6 @@ int64_t sg_scratch_words(int64_t nreg);
 const int64_t* sg_total_slot(const SgCall& c);
 int sg_count(const SgCall& c, hipStream_t s);
 int sg_write(const SgCall& c, int64_t cap, int64_t* d_off, sccg_segment* d_seg, hipStream_t s);
+// The calls' scan, one launch of one block under the fetch family: out[k] = in[0] + .. + in[k - 1], k <= m
+// (lift.hip's flat work space is laid out by it too).
+int sg_scan(const int64_t* in, int64_t* out, int64_t m, hipStream_t s);

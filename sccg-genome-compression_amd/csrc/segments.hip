@@ -389,6 +389,12 @@ const int64_t* sg_total_slot(const SgCall& c) {
     return A.woff + A.W;
 }
 
+int sg_scan(const int64_t* in, int64_t* out, int64_t m, hipStream_t s) {
+    PROF_LAUNCH(PROF_FETCH, s, k_sg_scan, dim3(1), dim3(SCCG_BLOCK), 0, s, in, out, m);
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
 int sg_count(const SgCall& c, hipStream_t s) {
     if (c.nreg <= 0) return SCCG_E_INVALID;
     const SgArgs A = sg_args(c);
@@ -396,11 +402,9 @@ int sg_count(const SgCall& c, hipStream_t s) {
     void (*const regions)(SgArgs) = c.src ? k_sg_regions<false> : k_sg_regions<true>;
     void (*const blocks)(SgArgs) = c.src ? k_sg_blocks<false, false> : k_sg_blocks<true, false>;
     PROF_LAUNCH(PROF_FETCH, s, regions, dim3(grid_for(A.n, SCCG_BLOCK)), blk, 0, s, A);
-    PROF_LAUNCH(PROF_FETCH, s, k_sg_scan, dim3(1), blk, 0, s, A.items, A.ioff, A.n);
+    if (const int rc = sg_scan(A.items, A.ioff, A.n, s)) return rc;
     PROF_LAUNCH(PROF_FETCH, s, blocks, dim3((unsigned)(A.W / WPB)), blk, 0, s, A);
-    PROF_LAUNCH(PROF_FETCH, s, k_sg_scan, dim3(1), blk, 0, s, A.wcnt, A.woff, A.W);
-    SCCG_HIP(hipGetLastError());
-    return 0;
+    return sg_scan(A.wcnt, A.woff, A.W, s);
 }
 
 int sg_write(const SgCall& c, int64_t cap, int64_t* d_off, sccg_segment* d_seg, hipStream_t s) {

@@ -209,6 +209,12 @@ def load_library():
         lib.sccg_reader_segments_device.argtypes = [vp, ctypes.POINTER(Region), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
         lib.sccg_cohort_segments.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, i64p, ctypes.POINTER(Buf)]
         lib.sccg_cohort_segments_device.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
+    if hasattr(lib, "sccg_reader_lift"):   # (absent from builds older than lift: A/B runs)
+        i64p = ctypes.POINTER(i64)
+        lib.sccg_reader_lift.argtypes = [vp, ctypes.POINTER(Region), sz, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_reader_lift_device.argtypes = [vp, ctypes.POINTER(Region), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
+        lib.sccg_cohort_lift.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_cohort_lift_device.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -706,6 +712,20 @@ class Reader:
         regions, arr = self._regions(regions)
         return _segments_tensor(self.ctx, self.lib.sccg_reader_segments_device, self.ptr, arr, len(regions), stream)
 
+    def lift(self, intervals):
+        """Intervals of the reference onto this sample, run-length coded (sccg_reader_lift): (off int64 [n + 1],
+        blk int64 [m, 3]) -- interval i's blocks are blk[off[i]:off[i + 1]], rows (ref, len, pos): `len`
+        reference bases from `ref` lie at sequence positions pos, pos + 1, ... (pos >= 0), have no copy (pos
+        LOCATE_NONE) or are one erased N run of the reference (pos LOCATE_REF_N); maximal, tiling the interval.
+        What locate() says per base.  Needs can_locate."""
+        intervals, arr = self._regions(intervals)
+        return _segments_host(self.ctx, self.lib.sccg_reader_lift, self.ptr, arr, len(intervals))
+
+    def lift_tensor(self, intervals, stream=None):
+        """lift() into torch tensors on the context's device."""
+        intervals, arr = self._regions(intervals)
+        return _segments_tensor(self.ctx, self.lib.sccg_reader_lift_device, self.ptr, arr, len(intervals), stream)
+
     def locate_tensor(self, ref_positions, stream=None):
         """locate() into torch tensors on the context's device: (pos int64 [n], copies int32 [n])."""
         import numpy as np
@@ -722,7 +742,7 @@ class Reader:
 
 
 def _segments_host(ctx, call, ptr, arr, n):
-    """(off int64 [n + 1], seg int64 [m, 3]) of a host segments call (sccg_*_segments)."""
+    """(off int64 [n + 1], seg int64 [m, 3]) of a host segments or lift call (sccg_*_segments, sccg_*_lift)."""
     import numpy as np
     off = np.zeros(n + 1, dtype=np.int64)
     buf = Buf()
@@ -733,7 +753,8 @@ def _segments_host(ctx, call, ptr, arr, n):
 
 
 def _segments_tensor(ctx, call, ptr, arr, n, stream):
-    """The same pair as device tensors (sccg_*_segments_device): one call to size, one into exactly-sized tensors."""
+    """The same pair as device tensors (sccg_*_segments_device, sccg_*_lift_device): one call to size, one into
+    exactly-sized tensors."""
     import torch
     dev = torch.device("cuda", ctx.device)
     s = torch.cuda.current_stream(dev) if stream is None else stream
@@ -855,6 +876,17 @@ class Cohort:
         """segments() into torch tensors on the context's device."""
         rows, arr = self._items(items)
         return _segments_tensor(self.ctx, self.lib.sccg_cohort_segments_device, self.ptr, arr, len(rows), stream)
+
+    def lift(self, items):
+        """Reader.lift over the cohort (sccg_cohort_lift): items (sample, begin, end) of each sample's reference.
+        A sample answers only if its reader had enable_locate() called before this cohort was created."""
+        rows, arr = self._items(items)
+        return _segments_host(self.ctx, self.lib.sccg_cohort_lift, self.ptr, arr, len(rows))
+
+    def lift_tensor(self, items, stream=None):
+        """lift() into torch tensors on the context's device."""
+        rows, arr = self._items(items)
+        return _segments_tensor(self.ctx, self.lib.sccg_cohort_lift_device, self.ptr, arr, len(rows), stream)
 
     @staticmethod
     def _loci(items):

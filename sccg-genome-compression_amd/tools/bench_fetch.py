@@ -30,7 +30,14 @@ of the same run, and Cohort.fetch_tensor_at beside the fetch_tensor it wraps.  -
 segments leg alone: sccg_reader_segments_device / sccg_cohort_segments_device at 1 x 1 Mb, 1000 x 1 kb,
 1 x 10 Mb and the whole sequence beside what they replace -- the origin fetch of the same regions plus a run-length coding of its
 output on the device in PyTorch -- interleaved call by call, with the segment counts and the bytes either
-writes; the segments are checked by expanding them back to the origin fetch's output.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
+writes; the segments are checked by expanding them back to the origin fetch's output.  --only-lift runs the
+lift leg alone: sccg_reader_lift_device / sccg_cohort_lift_device at 1 x 1 kb, 1 x 1 Mb, 1000 x 1 kb of the
+reference and the whole reference beside what they replace -- the locate call of every position of the intervals
+plus a run-length coding of its output on the device in PyTorch (not at the whole reference: its query list
+alone is 8 bytes per base) -- and, as yardsticks, the locate call alone and the segments call over sequence
+regions of the same sizes, interleaved call by call, with the block counts and the bytes either writes; the
+blocks are checked row for row against that coding (the whole reference: expanded at 100,000 random
+positions against locate).  Every shape's bytes are checked against the target FASTA (an origin r >= 0
 must name the reference base the target's base is, -2 an N).  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
@@ -449,6 +456,126 @@ def segments_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_re
     return out
 
 
+def lift_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, rec_len, rfa, S=8):
+    """The lift call beside locate of every position + a run-length coding in PyTorch, reader and S-sample cohort."""
+    s = stream.cuda_stream
+    out = {"samples": S, "same_record": True, "shapes": {}}
+    ref = ctx.open_reference_device(d_ref.data_ptr(), ref_len, stream=s, coords=True)
+    readers = [ref.open_reader_device(d_rec.data_ptr(), rec_len, s) for _ in range(S)]
+    for r in readers:
+        r.enable_locate()
+    rd, co = readers[0], sccg.Cohort(readers)
+    L = rd.length
+    nR = len(rfa.partition(b"\n")[2].replace(b"\n", b""))
+    rng = random.Random(9)
+    PER_BASE = 16_000_000   # the most bases the per-base legs are run at
+    for name, (n, ln) in {"1x1kb": (1, 1000), "1x1Mb": (1, 1_000_000), "1000x1kb": (1000, 1000), "1xwhole": (1, nR)}.items():
+        begins = [rng.randrange(nR - ln + 1) for _ in range(n)]
+        samp = [k % S for k in range(n)]
+        rng.shuffle(samp)
+        F = n * ln
+        per_base = F <= PER_BASE
+        flat = (sccg.Region * n)(*[(b, b + ln) for b in begins])
+        items = (sccg.CohortRegion * n)(*[(b, b + ln, sm, 0) for b, sm in zip(begins, samp)])
+        sl = min(ln, L)   # the segments yardstick: sequence regions of the same sizes
+        sflat = (sccg.Region * n)(*[(min(b, L - sl), min(b, L - sl) + sl) for b in begins])
+        sitems = (sccg.CohortRegion * n)(*[(min(b, L - sl), min(b, L - sl) + sl, sm, 0) for b, sm in zip(begins, samp)])
+        q = np.concatenate([np.arange(b, b + ln, dtype=np.int64) for b in begins]) if per_base else None
+        qp = q.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if per_base else None
+        d_pos = torch.empty(F if per_base else 1, dtype=torch.int64, device=dev)
+        d_beg = torch.tensor(begins, dtype=torch.int64, device=dev)
+        got = ctypes.c_size_t()
+        for who in ("reader", "cohort"):
+            lift_call = lib.sccg_reader_lift_device if who == "reader" else lib.sccg_cohort_lift_device
+            seg_call = lib.sccg_reader_segments_device if who == "reader" else lib.sccg_cohort_segments_device
+            h, regs, sregs = (rd.ptr, flat, sflat) if who == "reader" else (co.ptr, items, sitems)
+            assert lift_call(h, regs, n, None, None, 0, ctypes.byref(got), s) == 0   # the size queries, outside the timing
+            m = got.value
+            assert seg_call(h, sregs, n, None, None, 0, ctypes.byref(got), s) == 0
+            ms = got.value
+            d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            d_blk = torch.empty((m, 3), dtype=torch.int64, device=dev)
+            d_seg = torch.empty((ms, 3), dtype=torch.int64, device=dev)
+            loci = None
+            if per_base and who == "cohort":
+                loci = (sccg.CohortLocus * F)()
+                view = np.frombuffer(loci, dtype=np.dtype([("r", "<i8"), ("s", "<i4"), ("f", "<u4")]))
+                view["r"], view["s"] = q, np.repeat(np.array(samp, dtype=np.int32), ln)
+            rle = [None]
+
+            def lift():
+                assert lift_call(h, regs, n, d_off.data_ptr(), d_blk.data_ptr(), m, ctypes.byref(got), s) == 0 and got.value == m
+
+            def size_query():
+                assert lift_call(h, regs, n, None, None, 0, ctypes.byref(got), s) == 0 and got.value == m
+
+            def segments():
+                assert seg_call(h, sregs, n, None, d_seg.data_ptr(), ms, ctypes.byref(got), s) == 0 and got.value == ms
+
+            def locate():
+                if who == "reader":
+                    rc = lib.sccg_reader_locate_device(h, qp, F, d_pos.data_ptr(), None, s)
+                else:
+                    rc = lib.sccg_cohort_locate_device(h, loci, F, d_pos.data_ptr(), None, s)
+                assert rc == 0, rc
+
+            def locate_rle():
+                locate()
+                o = d_pos.view(n, ln)
+                start = torch.ones((n, ln), dtype=torch.bool, device=dev)
+                start[:, 1:] = ~torch.where(o[:, :-1] >= 0, o[:, 1:] == o[:, :-1] + 1, o[:, 1:] == o[:, :-1])
+                at = torch.nonzero(start.view(-1)).view(-1)   # (a host wait for the count, as the lift call's one read)
+                end = torch.cat([at[1:], torch.tensor([F], dtype=torch.int64, device=dev)])
+                row = torch.div(at, ln, rounding_mode="floor")
+                rle[0] = torch.stack([d_beg[row] + (at - row * ln), end - at, d_pos[at]], dim=1)
+
+            calls = {"lift": lift, "size_query": size_query, "segments_same_sizes": segments}
+            if per_base:
+                calls.update({"locate": locate, "locate_plus_rle": locate_rle})
+            ev = {k: [] for k in calls}
+            for i in range(a.warmup + a.calls):   # interleaved: every leg once per round
+                for k, call in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    e0.record(stream)
+                    call()
+                    e1.record(stream)
+                    stream.synchronize()
+                    if i >= a.warmup:
+                        ev[k].append(e0.elapsed_time(e1))
+            ctx.profile(True, families=["fetch"])
+            for _ in range(a.calls):
+                lift()
+            kern = ctx.profile_get().get("fetch", (0.0, 0))
+            ctx.profile(False)
+            ln_ = d_blk[:, 1]
+            exact = bool(int(ln_.sum()) == F and int(d_off[-1]) == m and bool((ln_ > 0).all()))
+            if per_base:
+                exact = exact and torch.equal(rle[0], d_blk)
+            else:   # expanded at random positions against locate (one interval: the block of r is the last with ref <= r)
+                qs = np.sort(np.array([rng.randrange(nR) for _ in range(100_000)], dtype=np.int64))
+                want = (rd.locate(qs)[0] if who == "reader" else co.locate([(samp[0], int(r)) for r in qs])[0])
+                blk = d_blk.cpu().numpy()
+                k = np.searchsorted(blk[:, 0], qs, side="right") - 1
+                exact = exact and bool(np.array_equal(np.where(blk[k, 2] >= 0, blk[k, 2] + (qs - blk[k, 0]), blk[k, 2]), want))
+            med = {k: statistics.median(v) for k, v in ev.items()}
+            row = {"bases": F, "blocks": m, "block_bytes": 24 * m + 8 * (n + 1), "locate_bytes": 8 * F, "segments_same_sizes": ms,
+                   "event_ms": {k: spread(v) for k, v in ev.items()}, "kernels_ms_per_call": round(kern[0] / a.calls, 4),
+                   "launches_per_call": kern[1] / a.calls, "exact": exact}
+            if per_base:
+                row["locate_over_lift"] = round(med["locate"] / med["lift"], 2)
+                row["locate_rle_over_lift"] = round(med["locate_plus_rle"] / med["lift"], 2)
+            out["shapes"][f"{name}/{who}"] = row
+            del d_off, d_blk, d_seg, loci
+            rle[0] = None
+        del d_pos, q
+    co.close()
+    for r in readers:
+        r.close()
+    ref.close()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", default="hg")
@@ -460,6 +587,7 @@ def main() -> None:
     ap.add_argument("--only-origin", action="store_true", help="the origin section alone")
     ap.add_argument("--only-locate", action="store_true", help="the locate section alone")
     ap.add_argument("--only-segments", action="store_true", help="the segments section alone")
+    ap.add_argument("--only-lift", action="store_true", help="the lift section alone")
     a = ap.parse_args()
     import torch
     import sccg
@@ -496,6 +624,14 @@ def main() -> None:
     code = [4] * 256
     for k, ch in enumerate(b"ACGT"):
         code[ch] = code[ch + 32] = k
+    if a.only_lift:
+        out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
+               "lift": lift_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), rfa)}
+        ctx.close()
+        print(json.dumps(out))
+        if not all(v["exact"] for v in out["lift"]["shapes"].values()):
+            raise SystemExit("bench_fetch: lift section: the blocks are not the run-length coding of locate's answers")
+        return
     if a.only_segments:
         out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
                "segments": segments_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h))}
