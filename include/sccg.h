@@ -39,6 +39,9 @@
  *                                       (no counterpart)
  * sccg_reader_lift / _device,         intervals of the reference onto a sample, run-length coded: what
  *   sccg_cohort_lift / _device          locate spells out per reference base (no counterpart)
+ * sccg_reader_find / _device,         where an IUPAC pattern occurs in regions of a sample, either strand
+ *   sccg_cohort_find / _device          (no counterpart)
+ *   (sccg_find_pattern_masks)
  *
  * Conventions: status ints (0 = OK); the library never calls exit(); host buffers it returns are
  * malloc'ed and released with sccg_buf_free.  One context per GPU; a context is not re-entrant;
@@ -560,6 +563,67 @@ int sccg_reader_lift_device(sccg_reader* reader, const sccg_region* intervals /*
 int sccg_cohort_lift(sccg_cohort* cohort, const sccg_cohort_region* intervals, size_t n, int64_t* off, sccg_buf* out);
 int sccg_cohort_lift_device(sccg_cohort* cohort, const sccg_cohort_region* intervals /*host*/, size_t n, void* d_off, void* d_blk,
                             size_t cap, size_t* n_blk, void* stream);
+
+/* Find: where a pattern -- a primer, a restriction site, a guide + PAM, a motif -- occurs in regions of a
+ * sample, on either strand.  The first reader call whose answer depends on the bases themselves: the regions
+ * are decoded and matched in one pass on the device, and no base is written to memory.
+ *
+ * The pattern is m letters, 1 <= m <= SCCG_FIND_MAX_PATTERN, of the IUPAC nucleotide alphabet
+ * ACGTURYSWKMBDHVN in either case (U means T).  A letter stands for a set of {A, C, G, T}, held as a 4-bit
+ * mask (bit 0 A, 1 C, 2 G, 3 T): R = AG, Y = CT, S = CG, W = AT, K = GT, M = AC, B = CGT, D = AGT, H = ACT,
+ * V = ACG, N = ACGT.  A sequence position j has code(j), SCCG_ENC_INDEX's: A/a 0, C/c 1, G/g 2, T/t 3, every
+ * other byte 4 -- a base of a target N run, a literal 'N' and any other byte alike.  The search is case-blind
+ * and never reads the lowercase runs.  CODE 4 MATCHES NO PATTERN LETTER, NOT EVEN 'N': the pattern letter N
+ * means "any of A, C, G, T", so a window holding an N base is never a hit.
+ *
+ * Position j of region [begin, end) is a forward hit iff j + m <= end and mask[t] has bit code(j + t) for
+ * every t < m: a window that would match but crosses `end` is no hit of that region.  It is a reverse hit iff
+ * the reverse complement of seq[j, j + m) matches the pattern, which is the forward window matching the
+ * reverse-complemented pattern (the masks reversed, A <-> T and C <-> G swapped in each); it is reported at
+ * the same pos = j, the leftmost forward coordinate, with strand 1.  A palindromic site such as GAATTC is
+ * hit on both strands at the same pos and gives two rows.  flags: SCCG_FIND_FWD searches the forward strand,
+ * SCCG_FIND_REV the reverse strand, both together both; 0 means forward only.
+ *
+ * The layout is sccg_*_segments*'s: the hits of region i are out[off[i], off[i + 1]), off[0] == 0, off[n]
+ * the total, in ascending pos, forward before reverse at equal pos; regions may be empty, shorter than m (no
+ * hits), repeat, overlap and come in any order; n == 0 is SCCG_OK with no hits (off[0] = 0).  The result is
+ * deterministic: the same call gives the same bytes.  The host forms return the sccg_hit array in *out
+ * (out->len bytes; sccg_buf_free) and, when `off` is given, the n + 1 offsets.  The _device forms write int64
+ * offsets to d_off (may be NULL) and hits to d_hit, device memory, on `stream` (a hipStream_t; NULL = the
+ * context's own): d_hit == NULL is a size query that only sets *n_hit; with cap (in hits) too small they
+ * return SCCG_E_NOMEM, *n_hit the number needed, the buffers' contents unspecified.  Both forms synchronise
+ * before returning.
+ *
+ * Any reader can be searched, private or shared, with or without reference coordinates; the locate index is
+ * not needed.  Costs: three kernel launches (two for a size query), one copy of the region list -- the masks
+ * travel in the kernel arguments -- and one host read (the total) per call, whatever n, the region sizes and
+ * the samples touched are.  The scratch (2 bits per candidate start) lives in the staging the call grows, as
+ * for segments; sccg_reader_device_bytes does not change.
+ *
+ * SCCG_E_INVALID, nothing written, sccg_last_error naming the first offender.  In this order: a NULL reader /
+ * cohort / out / n_hit (no message); a NULL pattern, m == 0, m > SCCG_FIND_MAX_PATTERN or a byte outside the
+ * alphabet ("pattern byte k"); a flag bit other than SCCG_FIND_FWD | SCCG_FIND_REV; d_off or d_hit not 8-byte
+ * aligned; then the regions as for segments: a NULL list with n > 0, a region outside 0 <= begin <= end <=
+ * length, in a cohort a sample outside [0, n_samples) or ANY flag bit of a region set, bit 0 included (the
+ * strands are the call's, not a region's).
+ *
+ * sccg_find_pattern_masks is a pure host function, no context: the m masks of a pattern in fwd and of its
+ * reverse complement in rev (either may be NULL), what the kernels are launched with; SCCG_E_INVALID as
+ * above. */
+#define SCCG_FIND_MAX_PATTERN 64
+#define SCCG_FIND_FWD 1u
+#define SCCG_FIND_REV 2u
+typedef struct { int64_t pos, strand; } sccg_hit;   /* strand 0 forward, 1 reverse */
+int sccg_find_pattern_masks(const char* pattern, size_t m, uint8_t* fwd /*m*/, uint8_t* rev /*m*/);
+int sccg_reader_find(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions, size_t n, uint32_t flags,
+                     int64_t* off /*host, n + 1; may be NULL*/, sccg_buf* out /*sccg_hit[]*/);
+int sccg_reader_find_device(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions /*host*/, size_t n,
+                            uint32_t flags, void* d_off /*int64[n + 1] or NULL*/, void* d_hit, size_t cap /*hits*/, size_t* n_hit,
+                            void* stream);
+int sccg_cohort_find(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n, uint32_t flags,
+                     int64_t* off, sccg_buf* out);
+int sccg_cohort_find_device(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions /*host*/, size_t n,
+                            uint32_t flags, void* d_off, void* d_hit, size_t cap, size_t* n_hit, void* stream);
 
 void sccg_buf_free(sccg_buf* b);
 

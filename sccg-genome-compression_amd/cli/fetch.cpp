@@ -15,6 +15,7 @@
 // N runs.  --origin together with -i is a usage error.
 // `fetch --locate ...` and `fetch --lift ...` (first argument only) ask the other way round, from the
 // reference to the sequence: locate_main and lift_main below.
+// `fetch --find <PATTERN> ...` (first argument only) asks where an IUPAC pattern occurs: find_main below.
 #include "cli_common.h"
 
 #include <cstring>
@@ -35,7 +36,8 @@ static bool parse_pos(const std::string& s, int64_t* v) {
 // tab-separated, 1-based; pos is `-` when no token copies the position and `N` inside an erased N run
 static int locate_main(int argc, char* argv[]) {
     const bool mixed = argc > 2 && (std::string(argv[2]) == "-i" || std::string(argv[2]) == "--reverse-complement" ||
-                                    std::string(argv[2]) == "--origin" || std::string(argv[2]) == "--lift");
+                                    std::string(argv[2]) == "--origin" || std::string(argv[2]) == "--lift" ||
+                                    std::string(argv[2]) == "--find");
     if (argc < 5 || mixed) {
         std::cerr << "Usage: " << argv[0] << " --locate <record_file> <reference_file> <refpos>...\n"
                   << "  refpos: a 1-based position of the reference sequence; prints refpos, the first 1-based sequence\n"
@@ -100,7 +102,7 @@ static int locate_main(int argc, char* argv[]) {
 // `rbegin rend N` for an erased N run of the reference
 static int lift_main(int argc, char* argv[]) {
     const std::string a2 = argc > 2 ? argv[2] : "";
-    const bool mixed = a2 == "-i" || a2 == "--reverse-complement" || a2 == "--origin" || a2 == "--locate";
+    const bool mixed = a2 == "-i" || a2 == "--reverse-complement" || a2 == "--origin" || a2 == "--locate" || a2 == "--find";
     if (argc < 5 || mixed) {
         std::cerr << "Usage: " << argv[0] << " --lift <record_file> <reference_file> <refregion>...\n"
                   << "  refregion: begin-end (1-based, inclusive) or pos, of the reference sequence; prints >begin-end, then\n"
@@ -171,7 +173,99 @@ static int lift_main(int argc, char* argv[]) {
     return 0;
 }
 
+// `fetch --find <PATTERN> <record_file> <reference_file> <region>...`: per region of the sequence (`begin-end`,
+// 1-based inclusive, or a bare `pos`) a line `>begin-end`, then one tab-separated line per hit of the IUPAC
+// pattern on either strand (sccg_reader_find): `pos strand bases` -- pos the 1-based leftmost position of the
+// window, strand `+` or `-`, bases the window as the sample carries it, forward strand (one ordinary fetch
+// of all hit windows).  A malformed pattern is a usage error before the GPU is touched.
+static int find_main(int argc, char* argv[]) {
+    const std::string pat = argc > 2 ? argv[2] : "";
+    const bool mixed = pat == "-i" || pat == "--reverse-complement" || pat == "--origin" || pat == "--locate" || pat == "--lift" ||
+                       pat == "--find";
+    const bool bad_pattern = argc > 2 && !mixed && sccg_find_pattern_masks(pat.data(), pat.size(), nullptr, nullptr) != SCCG_OK;
+    if (argc < 6 || mixed || bad_pattern) {
+        if (bad_pattern)
+            std::cerr << "Error: malformed pattern '" << pat << "' (1 to " << SCCG_FIND_MAX_PATTERN
+                      << " IUPAC nucleotide letters, ACGTURYSWKMBDHVN in either case)\n";
+        std::cerr << "Usage: " << argv[0] << " --find <PATTERN> <record_file> <reference_file> <region>...\n"
+                  << "  PATTERN: 1 to " << SCCG_FIND_MAX_PATTERN << " IUPAC nucleotide letters (N: any of A, C, G, T); both strands are searched\n"
+                  << "  region: begin-end (1-based, inclusive) or pos; prints >begin-end, then one line per hit:\n"
+                  << "      pos strand(+|-) bases -- the window's leftmost position and its bases on the forward strand\n"
+                  << "  --find is the first argument only, not with -i, --origin, --locate or --lift\n";
+        return 1;
+    }
+    std::vector<sccg_region> regions;
+    for (int i = 5; i < argc; i++) {
+        const std::string a = argv[i];
+        const size_t dash = a.find('-');
+        int64_t b = 0, e = 0;
+        const bool ok = dash == std::string::npos ? parse_pos(a, &b) && (e = b, true)
+                                                  : parse_pos(a.substr(0, dash), &b) && parse_pos(a.substr(dash + 1), &e);
+        if (!ok || b < 1 || e < b) {
+            std::cerr << "Error: malformed region '" << a << "' (begin-end, 1-based, inclusive, begin <= end)\n";
+            return 1;
+        }
+        regions.push_back(sccg_region{b - 1, e});
+    }
+    std::string ref, rec;
+    if (!slurp(argv[4], ref)) {
+        std::cerr << "Greska pri otvaranju reference: " << argv[4] << "\n";
+        return 1;
+    }
+    if (!slurp(argv[3], rec)) {
+        std::cerr << "Greska pri otvaranju datoteke: " << argv[3] << "\n";
+        return 1;
+    }
+    sccg_ctx* ctx = nullptr;
+    int rc = sccg_ctx_create(cli_device(), &ctx);
+    if (rc) {
+        std::cerr << "Error: no usable GPU (sccg_ctx_create rc=" << rc << ")\n";
+        return 1;
+    }
+    sccg_reader* rd = nullptr;
+    rc = sccg_reader_open(ctx, ref.data(), ref.size(), rec.data(), rec.size(), &rd);
+    if (rc) {
+        std::cerr << "Error opening the record: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    sccg_buf hits{}, bases{};
+    std::vector<int64_t> off(regions.size() + 1);
+    std::vector<sccg_hit> hit;
+    rc = sccg_reader_find(rd, pat.data(), pat.size(), regions.data(), regions.size(), SCCG_FIND_FWD | SCCG_FIND_REV, off.data(), &hits);
+    if (!rc) {   // the windows of all hits in one fetch
+        hit.resize(hits.len / sizeof(sccg_hit));
+        if (!hit.empty()) memcpy(hit.data(), hits.data, hit.size() * sizeof(sccg_hit));
+        std::vector<sccg_region> win(hit.size());
+        for (size_t k = 0; k < hit.size(); k++) win[k] = sccg_region{hit[k].pos, hit[k].pos + (int64_t)pat.size()};
+        rc = sccg_reader_fetch(rd, win.data(), win.size(), 0, &bases);
+    }
+    if (rc) {
+        std::cerr << "Error finding: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_buf_free(&hits);
+        sccg_reader_close(rd);
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    std::string out;
+    for (size_t i = 0; i < regions.size(); i++) {
+        out += ">" + std::to_string(regions[i].begin + 1) + "-" + std::to_string(regions[i].end) + "\n";
+        for (int64_t k = off[i]; k < off[i + 1]; k++) {
+            out += std::to_string(hit[(size_t)k].pos + 1) + "\t" + (hit[(size_t)k].strand ? "-" : "+") + "\t";
+            out.append(bases.data + (size_t)k * pat.size(), pat.size());
+            out += '\n';
+        }
+    }
+    std::cout << out;
+    sccg_buf_free(&hits);
+    sccg_buf_free(&bases);
+    sccg_reader_close(rd);
+    sccg_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
+    if (argc > 1 && std::string(argv[1]) == "--find") return find_main(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "--lift") return lift_main(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "--locate") return locate_main(argc, argv);
     const bool rc_flag = argc > 1 && (std::string(argv[1]) == "-i" || std::string(argv[1]) == "--reverse-complement");
@@ -179,7 +273,7 @@ int main(int argc, char* argv[]) {
     const int a0 = rc_flag || origin ? 2 : 1;   // the first file argument
     const bool both = argc > 2 && ((origin && (std::string(argv[2]) == "-i" || std::string(argv[2]) == "--reverse-complement")) ||
                                    (rc_flag && std::string(argv[2]) == "--origin") ||
-                                   ((origin || rc_flag) && std::string(argv[2]) == "--lift"));
+                                   ((origin || rc_flag) && (std::string(argv[2]) == "--lift" || std::string(argv[2]) == "--find")));
     if (argc < a0 + 3 || both) {
         std::cerr << "Usage: " << argv[0] << " [-i | --origin] <record_file> <reference_file> <region>...\n"
                   << "  region: begin-end (1-based, inclusive) or pos\n"

@@ -32,7 +32,9 @@
 
 #include "internal.h"
 #include "decomp.h"
+#include "find.h"
 #include "recparse.h"
+#include "segments.h"
 
 namespace {
 
@@ -1497,6 +1499,185 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_fetch_origin(const FetchArgs A) 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Find (sccg_*_find*): where an IUPAC pattern of m <= 64 letters occurs in the regions, on either
+// strand.  The fetch kernels' front with another flat space and another epilogue: the flat space is
+// counted in candidate starts -- region i owns max(0, len_i - m + 1) of them, so a window never
+// crosses its region's end -- and a wave owns FD_TILE = 960 consecutive ones, a lane 16, as
+// fetch_spans hands them out.  For each span of starts [j0, j1) the wave decodes the window
+// [j0, j1 + m - 1), at most FD_TILE + 63 <= FT_W positions, through fetch_decode_span into its LDS
+// tile; nothing of it goes to memory.
+//   pack    lane l walks positions j0 + 16 l .. + 15 through the target's N runs (NCursor) and packs
+//           their one-hot nibbles -- A 1, C 2, G 4, T 8, every other byte and every N 0 -- into one
+//           64-bit word of the wave's LDS, position j0 + s at nibble s % 16 of word s / 16.
+//   match   the pattern is up to four words of mask nibbles per strand (the reverse strand's: the
+//           masks reversed and complemented, so a reverse hit is a forward match of that pattern at
+//           the same position), in the kernel arguments.  A lane loads the six words around its
+//           first start, shifts them to that start, and for each of its starts r shifts by r more
+//           nibbles (constant shifts): a stretch of 16 letters matches iff no nibble of `seq & mask`
+//           is zero among the pattern's letters -- one AND, three shift-ORs and a compare a word.
+//           A lane's hits are two bits per start: forward at bit k, reverse at bit 16 + k of one
+//           32-bit word for its 16 flat slots, kept in a register across the tile's spans.
+//   k_find_count  leaves that word per lane (256 bytes a tile: 2 bits per candidate, against the
+//           byte per base an index fetch writes) and the tile's hit count; sg_scan makes the counts
+//           offsets; k_find_write expands the words -- the spans again for the positions, no decode
+//           -- into rows {pos, strand} in flat order, which is the order asked for: ascending pos
+//           within a region, forward before reverse.  off[i] = the hits before the region's first
+//           candidate, read from the same words by a thread per region, so regions that own no
+//           candidate (empty, shorter than m) get theirs like every other: the hits before flat
+//           position pre[i], or the total when pre[i] is the end of the space.
+// LDS per block: WPB x (FT_W + FD_WORDS x 8 + 2 x TK_B) = 6,912 bytes; k_find_count's 88 VGPRs, not
+// LDS, set its occupancy: 5 waves per SIMD.  Every loop is bounded by a data size; no wave waits for another.
+// ---------------------------------------------------------------------------------------------
+constexpr int FD_MAXM = SCCG_FIND_MAX_PATTERN;
+constexpr int FD_TILE = (FT_W - (FD_MAXM - 1)) / OPT * OPT;   // candidate starts of a wave: whole lanes of OPT
+constexpr int FD_WORDS = FT_W / 16 + 8;                       // packed words of a window, and the six a lane loads past its own
+static_assert(OPT == 16, "a lane's starts are one 16-bit mask a strand, its bases one 64-bit word");
+static_assert(FD_TILE + FD_MAXM - 1 <= FT_W, "a span's window fits fetch_decode_span's bound and the LDS tile");
+static_assert(FD_TILE / 16 + 6 <= FD_WORDS, "the words a lane loads exist");
+
+struct FindArgs {
+    FetchArgs F;                        // pre: the prefix of the regions' candidates, F.F all of them; forward, no out
+    uint64_t pf[4], pr[4], lm[4];       // mask nibbles of the pattern, of its reverse complement; 1 per letter
+    int32_t m, nw;                      // letters, words holding them
+    uint32_t fwd, rev;                  // strands searched
+    int64_t W;                          // tiles (>= 1)
+    uint32_t* bits;                     // W * 64: a lane's hits
+    int64_t* wcnt;                      // W: hits per tile (the count)
+    int64_t* woff;                      // W + 1: their exclusive prefix (the scan's output, the write's input)
+    int64_t* off;                       // nreg + 1 or null
+    sccg_hit* hit;
+    int64_t cap;
+};
+
+// nibbles [nib, nib + 16) of hi:lo
+__device__ __forceinline__ uint64_t nib_shr(uint64_t lo, uint64_t hi, int nib) {
+    return nib ? (lo >> (4 * nib)) | (hi << (64 - 4 * nib)) : lo;
+}
+// bit 0 of every nibble that is not zero
+__device__ __forceinline__ uint64_t nib_any(uint64_t x) {
+    x |= x >> 1;
+    x |= x >> 2;
+    return x & 0x1111111111111111ull;
+}
+
+__device__ __forceinline__ FetchTile find_tile(const FindArgs& A, int64_t w) {
+    const int64_t base = w * FD_TILE;
+    return FetchTile{base, base, base + FD_TILE < A.F.F ? base + FD_TILE : A.F.F};
+}
+
+template <bool COHORT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_find_count(const FindArgs A) {
+    __shared__ uint8_t tile[WPB][FT_W];
+    __shared__ uint64_t pack[WPB][FD_WORDS];
+    __shared__ uint8_t stg[WPB][2 * TK_B];
+    const int64_t w = (int64_t)blockIdx.x * WPB + wave_in_block();
+    if (w >= A.W) return;
+    const int lane = lane_id();
+    uint8_t* sdec = tile[wave_in_block()];
+    uint64_t* pk = pack[wave_in_block()];
+    uint8_t* st = stg[wave_in_block()];
+    const FetchTile T = find_tile(A, w);
+    if (lane < FD_WORDS - 64) pk[64 + lane] = 0;   // (read by the last lanes, masked by the pattern's end)
+    uint32_t bits = 0;
+    if (T.w0 < T.fend)
+        fetch_spans<COHORT>(A.F, T, [&](const DcCohortEntry& E, int64_t j0, int64_t j1, bool, int64_t j, int k0, int k1) {
+            const int64_t je = j1 + (A.m - 1);   // <= the region's end: j1 - 1 is a candidate
+            const FetchSpan sp = fetch_decode_span(E.S, j0, je, sdec, st);
+            int64_t q = j0 + (int64_t)lane * 16;
+            uint64_t word = 0;
+            if (q < je) {
+                NCursor N(E, sp.rn0);
+                const int cnt = je - q < 16 ? (int)(je - q) : 16;
+                for (int t = 0; t < cnt; t++) {
+                    N.seek(q);
+                    const uint32_t c = q >= N.s ? 4u : base_code(sdec[q - N.b - sp.d0]);
+                    if (c < 4u) word |= (uint64_t)(1u << c) << (4 * t);
+                    q++;
+                }
+            }
+            pk[lane] = word;
+            wave_sync();
+            if (k0 < k1) {
+                const int s0 = (int)(j - j0), a = s0 >> 4, sh = s0 & 15, cnt = k1 - k0;
+                uint64_t raw[6], v[5];
+#pragma unroll
+                for (int k = 0; k < 6; k++) raw[k] = pk[a + k];
+#pragma unroll
+                for (int k = 0; k < 5; k++) v[k] = nib_shr(raw[k], raw[k + 1], sh);
+                uint32_t hf = 0, hr = 0;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    bool f = A.fwd != 0, rv = A.rev != 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (k < A.nw) {
+                            const uint64_t x = nib_shr(v[k], v[k + 1], r);
+                            f = f && nib_any(x & A.pf[k]) == A.lm[k];
+                            rv = rv && nib_any(x & A.pr[k]) == A.lm[k];
+                        }
+                    if (r < cnt) {
+                        hf |= (uint32_t)f << r;
+                        hr |= (uint32_t)rv << r;
+                    }
+                }
+                bits |= (hf << k0) | (hr << (16 + k0));
+            }
+        });
+    A.bits[w * 64 + lane] = bits;
+    const int64_t total = wave_sum((int64_t)__popc(bits));
+    if (lane == 0) A.wcnt[w] = total;
+}
+
+template <bool COHORT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_find_write(const FindArgs A) {
+    // the regions' offsets: the hits before flat position pre[i]
+    if (A.off) {
+        const int64_t total = A.woff[A.W];
+        for (int64_t i = (int64_t)blockIdx.x * SCCG_BLOCK + threadIdx.x; i <= A.F.nreg; i += (int64_t)gridDim.x * SCCG_BLOCK) {
+            const int64_t f = A.F.pre[i];
+            int64_t o = total;
+            if (f < A.F.F) {
+                const int64_t w = f / FD_TILE;
+                const int sl = (int)(f - w * FD_TILE);
+                const uint32_t* __restrict__ b = A.bits + w * 64;
+                o = A.woff[w];
+                for (int l = 0; l < (sl >> 4); l++) o += __popc(b[l]);
+                const uint32_t low = (1u << (sl & 15)) - 1u;
+                o += __popc(b[sl >> 4] & (low | (low << 16)));
+            }
+            A.off[i] = o;
+        }
+    }
+    const int64_t w = (int64_t)blockIdx.x * WPB + wave_in_block();
+    if (w >= A.W) return;
+    const FetchTile T = find_tile(A, w);
+    if (T.w0 >= T.fend) return;
+    const uint32_t bits = A.bits[w * 64 + lane_id()];
+    const uint32_t c = (uint32_t)__popc(bits);
+    int64_t o = A.woff[w] + (wave_incl_add_dpp(c) - c);   // the lane's first row
+    if (!__ballot(c != 0)) return;
+    sccg_hit* __restrict__ hit = A.hit;
+    const int64_t cap = A.cap;
+    fetch_spans<COHORT>(A.F, T, [&](const DcCohortEntry&, int64_t, int64_t, bool, int64_t j, int k0, int k1) {
+        if (k0 >= k1) return;
+        uint32_t mk = (bits | (bits >> 16)) & ((1u << k1) - (1u << k0));   // the span's slots with a hit
+        while (mk) {
+            const int k = __ffs((int)mk) - 1;
+            mk &= mk - 1;
+            const int64_t pos = j + (k - k0);
+            if ((bits >> k) & 1u) {
+                if (o < cap) hit[o] = sccg_hit{pos, 0};
+                o++;
+            }
+            if ((bits >> (16 + k)) & 1u) {
+                if (o < cap) hit[o] = sccg_hit{pos, 1};
+                o++;
+            }
+        }
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
 // The R' -> R map of a shared reference: the maximal runs of the byte 'N' (uppercase only: a
 // lowercase 'n' survives into R' as "N", decompression.cpp:108 before :110) in the stripped,
 // original-case reference R.  A block takes RM_TILE bytes, a thread 16 of them in one load; a run
@@ -1815,6 +1996,66 @@ int dc_fetch(const DcFetch& c, hipStream_t s) {
     A.out = c.d_out;
     const int64_t nblk = (c.F - A.o_first + OB - 1) / OB;
     PROF_LAUNCH(PROF_FETCH, s, kernel, dim3((unsigned)nblk), dim3(SCCG_BLOCK), 0, s, A);
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
+namespace {
+int64_t fd_tiles(int64_t F) { return F > 0 ? (F + FD_TILE - 1) / FD_TILE : 1; }
+
+// scratch: W * 64 hit words (32 W int64), W counts, W + 1 offsets
+FindArgs fd_args(const FdCall& c) {
+    FindArgs A{};
+    if (c.src) A.F.E = DcCohortEntry{*c.src, c.src->nr.n, c.src->lr.n, c.src->nr.total};
+    A.F.tab = c.d_tab;
+    A.F.pre = c.d_pre;
+    A.F.beg = c.d_beg;
+    A.F.samp = c.d_samp;
+    A.F.nreg = c.nreg;
+    A.F.F = c.F;
+    for (int t = 0; t < c.m; t++) {
+        A.pf[t >> 4] |= (uint64_t)(c.fwd[t] & 15) << (4 * (t & 15));
+        A.pr[t >> 4] |= (uint64_t)(c.rev[t] & 15) << (4 * (t & 15));
+        A.lm[t >> 4] |= 1ull << (4 * (t & 15));
+    }
+    A.m = c.m;
+    A.nw = (c.m + 15) / 16;
+    A.fwd = c.want_fwd ? 1u : 0u;
+    A.rev = c.want_rev ? 1u : 0u;
+    A.W = fd_tiles(c.F);
+    int64_t* p = c.d_scratch;
+    A.bits = reinterpret_cast<uint32_t*>(p); p += 32 * A.W;
+    A.wcnt = p; p += A.W;
+    A.woff = p;
+    return A;
+}
+}  // namespace
+
+int64_t fd_candidates(int64_t len, int m) { return len >= m ? len - m + 1 : 0; }
+int64_t fd_scratch_words(int64_t F) { return 34 * fd_tiles(F) + 1; }
+
+const int64_t* fd_total_slot(const FdCall& c) {
+    const FindArgs A = fd_args(c);
+    return A.woff + A.W;
+}
+
+int fd_count(const FdCall& c, hipStream_t s) {
+    if (c.nreg <= 0 || c.m < 1 || c.m > FD_MAXM || c.F < 0) return SCCG_E_INVALID;
+    const FindArgs A = fd_args(c);
+    void (*const kernel)(FindArgs) = c.src ? k_find_count<false> : k_find_count<true>;
+    PROF_LAUNCH(PROF_FETCH, s, kernel, dim3((unsigned)((A.W + WPB - 1) / WPB)), dim3(SCCG_BLOCK), 0, s, A);
+    SCCG_HIP(hipGetLastError());
+    return sg_scan(A.wcnt, A.woff, A.W, s);
+}
+
+int fd_write(const FdCall& c, int64_t cap, int64_t* d_off, sccg_hit* d_hit, hipStream_t s) {
+    if (c.nreg <= 0 || c.m < 1 || c.m > FD_MAXM || c.F < 0 || cap < 0) return SCCG_E_INVALID;
+    FindArgs A = fd_args(c);
+    A.off = d_off;
+    A.hit = d_hit;
+    A.cap = cap;
+    void (*const kernel)(FindArgs) = c.src ? k_find_write<false> : k_find_write<true>;
+    PROF_LAUNCH(PROF_FETCH, s, kernel, dim3((unsigned)((A.W + WPB - 1) / WPB)), dim3(SCCG_BLOCK), 0, s, A);
     SCCG_HIP(hipGetLastError());
     return 0;
 }

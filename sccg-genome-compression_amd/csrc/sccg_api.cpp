@@ -36,6 +36,7 @@
 #include "internal.h"
 #include "locate.h"
 #include "segments.h"
+#include "find.h"
 #include "lift.h"
 
 static thread_local char g_hip_err[512];
@@ -2268,6 +2269,162 @@ int cohort_lift_check(sccg_cohort* co, const sccg_cohort_region* iv, size_t n, i
     return SCCG_OK;
 }
 
+// -------------------------------------------------------------------------------------------
+// find (sccg_*_find): where an IUPAC pattern occurs in the regions -- segments' calling rules (size query,
+// capacity, alignment, segments_none) over find.h's launchers and the flat space of candidate starts
+// -------------------------------------------------------------------------------------------
+// the mask of a pattern letter (bit 0 A, 1 C, 2 G, 3 T), 0 for a byte outside the alphabet (clearing bit 5
+// maps a lowercase letter onto its capital and no other byte onto a letter)
+uint8_t find_letter_mask(unsigned char ch) {
+    switch (ch & 0xDFu) {
+    case 'A': return 1;
+    case 'C': return 2;
+    case 'G': return 4;
+    case 'T': case 'U': return 8;
+    case 'R': return 1 | 4;
+    case 'Y': return 2 | 8;
+    case 'S': return 2 | 4;
+    case 'W': return 1 | 8;
+    case 'K': return 4 | 8;
+    case 'M': return 1 | 2;
+    case 'B': return 2 | 4 | 8;
+    case 'D': return 1 | 4 | 8;
+    case 'H': return 1 | 2 | 8;
+    case 'V': return 1 | 2 | 4;
+    case 'N': return 15;
+    default: return 0;
+    }
+}
+// fwd[t] = the mask of pattern[t]; rev = the reverse complement's (a complement swaps A <-> T, C <-> G: the four
+// bits reversed); either may be null.  Returns -1, or the index of the first byte outside the alphabet (the
+// lengths are the caller's to check)
+int64_t find_masks(const char* pattern, size_t m, uint8_t* fwd, uint8_t* rev) {
+    for (size_t t = 0; t < m; t++) {
+        const uint8_t k = find_letter_mask((unsigned char)pattern[t]);
+        if (!k) return (int64_t)t;
+        if (fwd) fwd[t] = k;
+        if (rev) rev[m - 1 - t] = (uint8_t)(((k & 1) << 3) | ((k & 2) << 1) | ((k & 4) >> 1) | ((k & 8) >> 3));
+    }
+    return -1;
+}
+
+// the pattern and the strand flags of a find call, the first of its checks, into the launchers' call
+int find_pattern_check(sccg_ctx* ctx, const char* pattern, size_t m, uint32_t flags, FdCall* c) {
+    if (!pattern) return ctx->fail(SCCG_E_INVALID, "null pattern");
+    if (m < 1 || m > SCCG_FIND_MAX_PATTERN)
+        return ctx->fail(SCCG_E_INVALID, "a pattern of %zu letters: 1 to %d are searched", m, SCCG_FIND_MAX_PATTERN);
+    const int64_t bad = find_masks(pattern, m, c->fwd, c->rev);
+    if (bad >= 0)
+        return ctx->fail(SCCG_E_INVALID, "pattern byte %lld (0x%02x) is no IUPAC nucleotide letter (ACGTURYSWKMBDHVN)", (long long)bad,
+                         (unsigned)(unsigned char)pattern[bad]);
+    if (flags & ~(SCCG_FIND_FWD | SCCG_FIND_REV)) return ctx->fail(SCCG_E_INVALID, "unknown find flag bits (flags %u)", flags);
+    c->m = (int)m;
+    c->want_fwd = !flags || (flags & SCCG_FIND_FWD);
+    c->want_rev = (flags & SCCG_FIND_REV) != 0;
+    return SCCG_OK;
+}
+
+// a cohort's regions: one pass, the first offender in list order decides; the strands are the call's
+int cohort_find_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n) {
+    sccg_ctx* ctx = co->ctx;
+    if (!regions && n) return ctx->fail(SCCG_E_INVALID, "null region list");
+    const int64_t ns = (int64_t)co->length.size();
+    for (size_t i = 0; i < n; i++) {
+        const sccg_cohort_region& r = regions[i];
+        if (r.flags)
+            return ctx->fail(SCCG_E_INVALID, "region %zu has flag bits set (flags %u): the call's flags choose the strands", i, r.flags);
+        if (r.sample < 0 || r.sample >= ns)
+            return ctx->fail(SCCG_E_INVALID, "region %zu names sample %d, outside [0, %lld)", i, (int)r.sample, (long long)ns);
+        const int64_t len = co->length[(size_t)r.sample];
+        if (r.begin < 0 || r.end < r.begin || r.end > len)
+            return ctx->fail(SCCG_E_INVALID, "region %zu [%lld, %lld) is outside sample %d's sequence [0, %lld)", i,
+                             (long long)r.begin, (long long)r.end, (int)r.sample, (long long)len);
+    }
+    return SCCG_OK;
+}
+
+// Pattern and regions validated, n > 0.  ONE pinned image -- [0, n] the exclusive prefix of the regions' candidate
+// starts (the flat space), (n, 2n] the begins, then, for a cohort, the samples as int32 -- in one copy, the scratch
+// behind it in the same allocation.  The three forms are segments_run's: d_hit given -- count, scan and write
+// queued back to back (the write is clipped to cap on the device) and the one host read of the total behind them,
+// which is the call's synchronise and its capacity check; d_hit NULL with h_out NULL -- the size query, two launches
+// and the read; h_out -- two launches, the read (it sizes the buffers), the write, one sync.
+template <typename Regions>
+int find_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, FdCall c, void* d_off, void* d_hit, size_t cap,
+             size_t* n_hit, int64_t* h_off, sccg_buf* h_out, hipStream_t s) {
+    constexpr bool samples = Regions::samples;
+    HIPTRY(hipSetDevice(ctx->device));
+    int64_t F = 0;
+    for (size_t i = 0; i < n; i++) {
+        const FetchItem r = regions(i);
+        F += fd_candidates(r.end - r.begin, c.m);
+    }
+    const size_t n4 = (n * sizeof(int32_t) + 7) & ~(size_t)7;
+    const size_t img = (2 * n + 1) * sizeof(int64_t) + (samples ? n4 : 0);
+    const size_t bytes = img + (size_t)fd_scratch_words(F) * sizeof(int64_t);
+    size_t rcap = 0;
+    hipError_t e = st.reserve_regions(bytes, &rcap);
+    if (e != hipSuccess) return reader_alloc_fail(ctx, e, rcap);
+    int64_t* h = st.h_reg;
+    int32_t* hs = reinterpret_cast<int32_t*>(h + 2 * n + 1);
+    int64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        const FetchItem r = regions(i);
+        h[i] = at;
+        h[n + 1 + i] = r.begin;
+        if (samples) hs[i] = r.sample;
+        at += fd_candidates(r.end - r.begin, c.m);
+    }
+    h[n] = at;
+    int64_t* d = reinterpret_cast<int64_t*>(st.d_reg);
+    HIPTRY(hipMemcpyAsync(d, h, img, hipMemcpyHostToDevice, s));
+    c.d_pre = d;
+    c.d_beg = d + n + 1;
+    c.d_samp = samples ? reinterpret_cast<const int32_t*>(d + 2 * n + 1) : nullptr;
+    c.nreg = (int64_t)n;
+    c.F = F;
+    c.d_scratch = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(d) + img);
+    TRY(fd_count(c, s));
+    if (!h_out && d_hit)   // (no host wait before it: slots beyond cap are not written, and such a call fails below)
+        TRY(fd_write(c, (int64_t)(cap < (size_t)INT64_MAX / 64 ? cap : (size_t)INT64_MAX / 64), reinterpret_cast<int64_t*>(d_off),
+                     reinterpret_cast<sccg_hit*>(d_hit), s));
+    int64_t total = 0;
+    {
+        const RbItem it{fd_total_slot(c), &total, (int)sizeof total};
+        TRY(dev_readback(&it, 1, s));   // (behind everything queued on s: the call's synchronise)
+    }
+    if (total < 0) return ctx->fail(SCCG_E_INTERNAL, "find: a count of %lld", (long long)total);
+    if (n_hit) *n_hit = (size_t)total;
+    if (!h_out) {
+        if (d_hit && (size_t)total > cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu hits", (size_t)total);
+        return SCCG_OK;
+    }
+    const size_t hit_bytes = (size_t)total * sizeof(sccg_hit), off_bytes = (n + 1) * sizeof(int64_t);
+    char* hb = (char*)malloc(hit_bytes + 1);
+    if (!hb) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
+    const auto fill = [&]() -> int {
+        size_t ocap = 0;
+        e = st.reserve_out(hit_bytes + off_bytes, &ocap);
+        if (e != hipSuccess) return reader_alloc_fail(ctx, e, ocap);
+        int64_t* o = reinterpret_cast<int64_t*>(st.d_out);   // the offsets, then the hits
+        TRY(fd_write(c, total, o, reinterpret_cast<sccg_hit*>(o + n + 1), s));
+        HIPTRY(hipStreamSynchronize(s));
+        if (hit_bytes) HIPTRY(hipMemcpy(hb, o + n + 1, hit_bytes, hipMemcpyDeviceToHost));
+        if (h_off) HIPTRY(hipMemcpy(h_off, o, off_bytes, hipMemcpyDeviceToHost));
+        return SCCG_OK;
+    };
+    const int rc = fill();
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        free(hb);
+        return rc;
+    }
+    hb[hit_bytes] = 0;
+    h_out->data = hb;
+    h_out->len = hit_bytes;
+    return SCCG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2787,6 +2944,69 @@ int sccg_cohort_lift(sccg_cohort* cohort, const sccg_cohort_region* intervals, s
     c.d_tab = reinterpret_cast<const LcSrc*>(cohort->d_ltab);
     return segments_run<LiftOps>(ctx, cohort->stage, CohortRegions{intervals}, n, c, bound, nullptr, nullptr, 0, nullptr, off, out,
                                  ctx->stream);
+}
+
+int sccg_find_pattern_masks(const char* pattern, size_t m, uint8_t* fwd, uint8_t* rev) {
+    if (!pattern || m < 1 || m > SCCG_FIND_MAX_PATTERN) return SCCG_E_INVALID;
+    return find_masks(pattern, m, fwd, rev) >= 0 ? SCCG_E_INVALID : SCCG_OK;
+}
+
+int sccg_reader_find_device(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions, size_t n, uint32_t flags,
+                            void* d_off, void* d_hit, size_t cap, size_t* n_hit, void* stream) {
+    if (!reader || !n_hit) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    FdCall c{};
+    int64_t F = 0;
+    int rc = find_pattern_check(ctx, pattern, m, flags, &c);
+    if (!rc) rc = segments_align_check(ctx, d_off, d_hit, "d_hit");
+    if (!rc) rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_hit ? d_off : nullptr, n_hit, nullptr, nullptr, s);
+    c.src = &reader->src;
+    return find_run(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, d_off, d_hit, cap, n_hit, nullptr, nullptr, s);
+}
+
+int sccg_reader_find(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions, size_t n, uint32_t flags,
+                     int64_t* off, sccg_buf* out) {
+    if (!reader || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    FdCall c{};
+    int64_t F = 0;
+    int rc = find_pattern_check(ctx, pattern, m, flags, &c);
+    if (!rc) rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;   // (nothing written: *out and off are the caller's as they were)
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    c.src = &reader->src;
+    return find_run(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
+}
+
+int sccg_cohort_find_device(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n,
+                            uint32_t flags, void* d_off, void* d_hit, size_t cap, size_t* n_hit, void* stream) {
+    if (!cohort || !n_hit) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    FdCall c{};
+    int rc = find_pattern_check(ctx, pattern, m, flags, &c);
+    if (!rc) rc = segments_align_check(ctx, d_off, d_hit, "d_hit");
+    if (!rc) rc = cohort_find_check(cohort, regions, n);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_hit ? d_off : nullptr, n_hit, nullptr, nullptr, s);
+    c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
+    return find_run(ctx, cohort->stage, CohortRegions{regions}, n, c, d_off, d_hit, cap, n_hit, nullptr, nullptr, s);
+}
+
+int sccg_cohort_find(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n, uint32_t flags,
+                     int64_t* off, sccg_buf* out) {
+    if (!cohort || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    FdCall c{};
+    int rc = find_pattern_check(ctx, pattern, m, flags, &c);
+    if (!rc) rc = cohort_find_check(cohort, regions, n);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
+    return find_run(ctx, cohort->stage, CohortRegions{regions}, n, c, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
 }
 
 // match_sequences seam (compression.cpp:36): local segments or the windowed global walk

@@ -28,6 +28,8 @@ DTYPES = {"u8": 0, "f16": 1, "bf16": 2, "f32": 3, "i32": 4}        # SCCG_DT_* (
 LOCATE_NONE = -1       # SCCG_LOCATE_NONE: no token copies the reference position (deleted, or a literal)
 LOCATE_REF_N = -2      # SCCG_LOCATE_REF_N: the position lies in an N run of the reference that R' has erased
 ORIGIN_LITERAL, ORIGIN_N = -1, -2                          # "origin" values that are no reference position
+FIND_MAX_PATTERN = 64                                      # SCCG_FIND_MAX_PATTERN
+FIND_STRANDS = {"+": 1, "-": 2, "both": 3}                 # SCCG_FIND_FWD, SCCG_FIND_REV, both
 ERRORS = {1: "SCCG_E_INVALID", 2: "SCCG_E_HIP", 3: "SCCG_E_NOMEM", 4: "SCCG_E_DELTA_STOI",
           5: "SCCG_E_FORMAT", 6: "SCCG_E_RANGE", 7: "SCCG_E_PARSE", 8: "SCCG_E_UNSUPPORTED",
           9: "SCCG_E_INTERNAL", 10: "SCCG_E_OPEN_REF", 11: "SCCG_E_OPEN_TGT", 12: "SCCG_E_WRITE"}
@@ -215,6 +217,13 @@ def load_library():
         lib.sccg_reader_lift_device.argtypes = [vp, ctypes.POINTER(Region), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
         lib.sccg_cohort_lift.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, i64p, ctypes.POINTER(Buf)]
         lib.sccg_cohort_lift_device.argtypes = [vp, ctypes.POINTER(CohortRegion), sz, vp, vp, sz, ctypes.POINTER(sz), vp]
+    if hasattr(lib, "sccg_reader_find"):   # (absent from builds older than find: A/B runs)
+        i64p, u8p, u32 = ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32
+        lib.sccg_find_pattern_masks.argtypes = [c, sz, u8p, u8p]
+        lib.sccg_reader_find.argtypes = [vp, c, sz, ctypes.POINTER(Region), sz, u32, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_reader_find_device.argtypes = [vp, c, sz, ctypes.POINTER(Region), sz, u32, vp, vp, sz, ctypes.POINTER(sz), vp]
+        lib.sccg_cohort_find.argtypes = [vp, c, sz, ctypes.POINTER(CohortRegion), sz, u32, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_cohort_find_device.argtypes = [vp, c, sz, ctypes.POINTER(CohortRegion), sz, u32, vp, vp, sz, ctypes.POINTER(sz), vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -726,6 +735,24 @@ class Reader:
         intervals, arr = self._regions(intervals)
         return _segments_tensor(self.ctx, self.lib.sccg_reader_lift_device, self.ptr, arr, len(intervals), stream)
 
+    def find(self, pattern, regions, strands="both"):
+        """Where an IUPAC pattern (str or bytes, 1 to FIND_MAX_PATTERN letters of ACGTURYSWKMBDHVN, case-blind)
+        occurs in the regions (sccg_reader_find): (off int64 [n + 1], hits int64 [h, 2]) -- region i's hits are
+        hits[off[i]:off[i + 1]], rows (pos, strand) in ascending pos, forward (0) before reverse (1); a reverse
+        hit is reported at the leftmost forward position of its window.  strands: "both", "+" or "-".  A
+        sequence base that is not A, C, G or T matches no letter, not even N."""
+        regions, arr = self._regions(regions)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_host(self.ctx, self.lib.sccg_reader_find, self.ptr, arr, len(regions), cols=2, head=(pat, len(pat)),
+                              mid=(flags,))
+
+    def find_tensor(self, pattern, regions, strands="both", stream=None):
+        """find() into torch tensors on the context's device."""
+        regions, arr = self._regions(regions)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_tensor(self.ctx, self.lib.sccg_reader_find_device, self.ptr, arr, len(regions), stream, cols=2,
+                                head=(pat, len(pat)), mid=(flags,))
+
     def locate_tensor(self, ref_positions, stream=None):
         """locate() into torch tensors on the context's device: (pos int64 [n], copies int32 [n])."""
         import numpy as np
@@ -741,34 +768,55 @@ class Reader:
         return pos, copies
 
 
-def _segments_host(ctx, call, ptr, arr, n):
-    """(off int64 [n + 1], seg int64 [m, 3]) of a host segments or lift call (sccg_*_segments, sccg_*_lift)."""
+def _segments_host(ctx, call, ptr, arr, n, cols=3, head=(), mid=()):
+    """(off int64 [n + 1], rows int64 [m, cols]) of a host segments, lift or find call (sccg_*_segments, sccg_*_lift,
+    sccg_*_find: head = its pattern arguments before the region list, mid = its flags behind it)."""
     import numpy as np
     off = np.zeros(n + 1, dtype=np.int64)
     buf = Buf()
-    rc = call(ptr, arr, n, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(buf))
+    rc = call(ptr, *head, arr, n, *mid, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(buf))
     if rc:
         ctx._err(rc)
-    return off, np.frombuffer(ctx._take(buf), dtype="<i8").reshape(-1, 3).copy()
+    return off, np.frombuffer(ctx._take(buf), dtype="<i8").reshape(-1, cols).copy()
 
 
-def _segments_tensor(ctx, call, ptr, arr, n, stream):
-    """The same pair as device tensors (sccg_*_segments_device, sccg_*_lift_device): one call to size, one into
-    exactly-sized tensors."""
+def _segments_tensor(ctx, call, ptr, arr, n, stream, cols=3, head=(), mid=()):
+    """The same pair as device tensors (sccg_*_segments_device, sccg_*_lift_device, sccg_*_find_device): one call to
+    size, one into exactly-sized tensors."""
     import torch
     dev = torch.device("cuda", ctx.device)
     s = torch.cuda.current_stream(dev) if stream is None else stream
     m = ctypes.c_size_t()
-    rc = call(ptr, arr, n, None, None, 0, ctypes.byref(m), s.cuda_stream or None)
+    rc = call(ptr, *head, arr, n, *mid, None, None, 0, ctypes.byref(m), s.cuda_stream or None)
     if rc:
         ctx._err(rc)
     off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    seg = torch.empty((m.value, 3), dtype=torch.int64, device=dev)
+    seg = torch.empty((m.value, cols), dtype=torch.int64, device=dev)
     if m.value:
-        rc = call(ptr, arr, n, off.data_ptr(), seg.data_ptr(), m.value, ctypes.byref(m), s.cuda_stream or None)
+        rc = call(ptr, *head, arr, n, *mid, off.data_ptr(), seg.data_ptr(), m.value, ctypes.byref(m), s.cuda_stream or None)
         if rc:
             ctx._err(rc)
     return off, seg
+
+
+def _find_args(pattern, strands):
+    """A find call's pattern as bytes and its strand flags."""
+    pat = pattern.encode("latin-1") if isinstance(pattern, str) else bytes(pattern)
+    if strands not in FIND_STRANDS:
+        raise ValueError(f'strands is "both", "+" or "-", not {strands!r}')
+    return pat, FIND_STRANDS[strands]
+
+
+def find_pattern_masks(pattern):
+    """The 4-bit masks (bit 0 A, 1 C, 2 G, 3 T) of an IUPAC pattern and of its reverse complement
+    (sccg_find_pattern_masks; no GPU): (fwd, rev), bytes of the pattern's length.  ValueError for a pattern that is
+    empty, longer than FIND_MAX_PATTERN or holds a byte outside ACGTURYSWKMBDHVN (either case)."""
+    lib = load_library()
+    pat = pattern.encode("latin-1") if isinstance(pattern, str) else bytes(pattern)
+    fwd, rev = (ctypes.c_uint8 * max(len(pat), 1))(), (ctypes.c_uint8 * max(len(pat), 1))()
+    if lib.sccg_find_pattern_masks(pat, len(pat), fwd, rev):
+        raise ValueError(f"not an IUPAC pattern of 1 to {FIND_MAX_PATTERN} letters: {pattern!r}")
+    return bytes(fwd[:len(pat)]), bytes(rev[:len(pat)])
 
 
 class Cohort:
@@ -887,6 +935,20 @@ class Cohort:
         """lift() into torch tensors on the context's device."""
         rows, arr = self._items(items)
         return _segments_tensor(self.ctx, self.lib.sccg_cohort_lift_device, self.ptr, arr, len(rows), stream)
+
+    def find(self, pattern, items, strands="both"):
+        """Reader.find over the cohort (sccg_cohort_find): items (sample, begin, end); the strands are the call's."""
+        rows, arr = self._items(items)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_host(self.ctx, self.lib.sccg_cohort_find, self.ptr, arr, len(rows), cols=2, head=(pat, len(pat)),
+                              mid=(flags,))
+
+    def find_tensor(self, pattern, items, strands="both", stream=None):
+        """find() into torch tensors on the context's device."""
+        rows, arr = self._items(items)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_tensor(self.ctx, self.lib.sccg_cohort_find_device, self.ptr, arr, len(rows), stream, cols=2,
+                                head=(pat, len(pat)), mid=(flags,))
 
     @staticmethod
     def _loci(items):

@@ -37,7 +37,11 @@ plus a run-length coding of its output on the device in PyTorch (not at the whol
 alone is 8 bytes per base) -- and, as yardsticks, the locate call alone and the segments call over sequence
 regions of the same sizes, interleaved call by call, with the block counts and the bytes either writes; the
 blocks are checked row for row against that coding (the whole reference: expanded at 100,000 random
-positions against locate).  Every shape's bytes are checked against the target FASTA (an origin r >= 0
+positions against locate).  --only-find runs the find leg alone: sccg_reader_find_device at 1 x 1 Mb, 1000 x 1 kb,
+1 x 10 Mb and the whole sequence and sccg_cohort_find_device at 1000 x 1 kb, both strands, for GAATTC, a 20-mer cut
+from the sample and N x 21 + GG, beside what the call replaces -- the index fetch of the same regions, then a
+PyTorch mask-table compare over m shifted slices and nonzero on the same stream -- interleaved call by call; every
+timed result is first checked equal to that baseline's rows.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
 must name the reference base the target's base is, -2 an N).  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
@@ -576,6 +580,100 @@ def lift_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, r
     return out
 
 
+def find_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, rec_len, truth, S=8):
+    """The find call beside what it replaces -- an index fetch, then a PyTorch mask-table compare over m shifted
+    slices and nonzero, on the same stream -- for one reader at four shapes and the S-sample cohort at 1000 x 1 kb."""
+    s = stream.cuda_stream
+    out = {"samples": S, "same_record": True, "shapes": {}}
+    ref = ctx.open_reference_device(d_ref.data_ptr(), ref_len, stream=s)
+    readers = [ref.open_reader_device(d_rec.data_ptr(), rec_len, s) for _ in range(S)]
+    rd, co = readers[0], sccg.Cohort(readers)
+    L = rd.length
+    rng = random.Random(7)
+    at = next(k for k in (rng.randrange(L - 20) for _ in range(10_000)) if all(c in b"ACGT" for c in truth[k:k + 20].upper()))
+    patterns = {"GAATTC": "GAATTC", "20mer": truth[at:at + 20].decode().upper(), "N21GG": "N" * 21 + "GG"}
+    out["patterns"] = patterns
+    shapes = [("1x1Mb", "reader", 1, 1_000_000), ("1000x1kb", "reader", 1000, 1000), ("1000x1kb", "cohort", 1000, 1000),
+              ("1x10Mb", "reader", 1, 10_000_000), ("1xwhole", "reader", 1, L)]
+    for name, who, n, ln in shapes:
+        begins = [rng.randrange(L - ln + 1) for _ in range(n)]
+        samp = [k % S for k in range(n)]
+        rng.shuffle(samp)
+        regions = [(b, b + ln) for b in begins]
+        flat = (sccg.Region * n)(*regions)
+        items = (sccg.CohortRegion * n)(*[(b, b + ln, sm, 0) for b, sm in zip(begins, samp)])
+        citems = [(sm, b, b + ln) for b, sm in zip(begins, samp)]
+        d_beg = torch.tensor(begins, dtype=torch.int64, device=dev)
+        call = lib.sccg_reader_find_device if who == "reader" else lib.sccg_cohort_find_device
+        h, regs = (rd.ptr, flat) if who == "reader" else (co.ptr, items)
+        got = ctypes.c_size_t()
+        for pname, pat in patterns.items():
+            pb, m = pat.encode(), len(pat)
+            fwd, rev = sccg.find_pattern_masks(pat)
+            mk = [torch.tensor(list(x), dtype=torch.uint8, device=dev) for x in (fwd, rev)]
+            assert call(h, pb, m, regs, n, 3, None, None, 0, ctypes.byref(got), s) == 0   # the size query, outside the timing
+            hits = got.value
+            d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            d_hit = torch.empty((max(hits, 1), 2), dtype=torch.int64, device=dev)
+            base = [None, None]
+
+            def find():
+                assert call(h, pb, m, regs, n, 3, d_off.data_ptr(), d_hit.data_ptr(), hits, ctypes.byref(got), s) == 0 and got.value == hits
+
+            def size_query():
+                assert call(h, pb, m, regs, n, 3, None, None, 0, ctypes.byref(got), s) == 0 and got.value == hits
+
+            def fetch_compare():
+                c = rd.fetch_tensor(regions, "index", stream=stream) if who == "reader" else co.fetch_tensor(citems, "index", stream=stream)
+                c = c.view(n, ln)
+                K = ln - m + 1
+                acc = torch.ones((n, K, 2), dtype=torch.bool, device=dev)
+                for t in range(m):   # a code's bit of the letter's mask; code 4 shifts every mask to 0
+                    w = c[:, t:t + K]
+                    acc[:, :, 0] &= (torch.bitwise_right_shift(mk[0][t], w) & 1).bool()
+                    acc[:, :, 1] &= (torch.bitwise_right_shift(mk[1][t], w) & 1).bool()
+                at = torch.nonzero(acc)   # (a host wait for the count, as the find call's one read): rows (region, start, strand)
+                base[0] = torch.stack([d_beg[at[:, 0]] + at[:, 1], at[:, 2]], dim=1)
+                base[1] = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(acc.sum(dim=(1, 2)), 0)])
+
+            fetch_compare()   # every timed result is first checked equal to the baseline's rows
+            find()
+            stream.synchronize()
+            exact = bool(torch.equal(base[0], d_hit[:hits]) and torch.equal(base[1], d_off))
+            calls = {"find": find, "size_query": size_query, "fetch_plus_compare": fetch_compare}
+            ev = {k: [] for k in calls}
+            for i in range(a.warmup + a.calls):   # interleaved: every leg once per round
+                for k, leg in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    e0.record(stream)
+                    leg()
+                    e1.record(stream)
+                    stream.synchronize()
+                    if i >= a.warmup:
+                        ev[k].append(e0.elapsed_time(e1))
+            exact = exact and bool(torch.equal(base[0], d_hit[:hits]) and torch.equal(base[1], d_off))
+            ctx.profile(True, families=["fetch"])
+            for _ in range(a.calls):
+                find()
+            kern = ctx.profile_get().get("fetch", (0.0, 0))
+            ctx.profile(False)
+            med = {k: statistics.median(v) for k, v in ev.items()}
+            out["shapes"][f"{name}/{who}/{pname}"] = {
+                "bases": n * ln, "hits": hits, "hit_bytes": 16 * hits + 8 * (n + 1), "index_bytes": n * ln,
+                "event_ms": {k: spread(v) for k, v in ev.items()}, "kernels_ms_per_call": round(kern[0] / a.calls, 4),
+                "launches_per_call": kern[1] / a.calls, "compare_over_find": round(med["fetch_plus_compare"] / med["find"], 2),
+                "exact": exact}
+            base[0] = base[1] = None
+            del d_off, d_hit
+            print(f"# find {name}/{who}/{pname}: {out['shapes'][f'{name}/{who}/{pname}']}", file=sys.stderr, flush=True)
+    co.close()
+    for r in readers:
+        r.close()
+    ref.close()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", default="hg")
@@ -588,6 +686,7 @@ def main() -> None:
     ap.add_argument("--only-locate", action="store_true", help="the locate section alone")
     ap.add_argument("--only-segments", action="store_true", help="the segments section alone")
     ap.add_argument("--only-lift", action="store_true", help="the lift section alone")
+    ap.add_argument("--only-find", action="store_true", help="the find section alone")
     a = ap.parse_args()
     import torch
     import sccg
@@ -624,6 +723,14 @@ def main() -> None:
     code = [4] * 256
     for k, ch in enumerate(b"ACGT"):
         code[ch] = code[ch + 32] = k
+    if a.only_find:
+        out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
+               "find": find_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth)}
+        ctx.close()
+        print(json.dumps(out))
+        if not all(v["exact"] for v in out["find"]["shapes"].values()):
+            raise SystemExit("bench_fetch: find section: the hits are not the rows of the fetch-and-compare baseline")
+        return
     if a.only_lift:
         out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
                "lift": lift_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), rfa)}
