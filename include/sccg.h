@@ -42,6 +42,8 @@
  * sccg_reader_find / _device,         where an IUPAC pattern occurs in regions of a sample, either strand
  *   sccg_cohort_find / _device          (no counterpart)
  *   (sccg_find_pattern_masks)
+ * sccg_reader_find_approx / _device,  the same within k substitutions, each hit with its mismatch count
+ *   sccg_cohort_find_approx / _device   (no counterpart)
  *
  * Conventions: status ints (0 = OK); the library never calls exit(); host buffers it returns are
  * malloc'ed and released with sccg_buf_free.  One context per GPU; a context is not re-entrant;
@@ -624,6 +626,44 @@ int sccg_cohort_find(sccg_cohort* cohort, const char* pattern, size_t m, const s
                      int64_t* off, sccg_buf* out);
 int sccg_cohort_find_device(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions /*host*/, size_t n,
                             uint32_t flags, void* d_off, void* d_hit, size_t cap, size_t* n_hit, void* stream);
+
+/* Find with mismatches: where the pattern occurs within max_mismatches substitutions (Hamming distance; no
+ * gaps) -- the off-target sites of a guide + PAM, the places a primer still binds.  Find's alphabet, masks,
+ * reverse-complement rule, codes, flags and layout; what differs is said here.
+ *
+ * For a candidate start j of a region, a strand s (0 forward, 1 reverse) and that strand's masks (the
+ * pattern's; the reverse-complemented pattern's), d(j, s) is the number of t < m where mask_s[t] lacks bit
+ * code(j + t).  CODE 4 -- a base of a target N run, a literal 'N', any other byte -- IS A MISMATCH AGAINST
+ * EVERY LETTER, 'N' INCLUDED.  (j, s) is a hit iff j + m <= end and d(j, s) <= K = max_mismatches: a window
+ * never crosses its region's end, whatever K is.  Rows are sccg_hit_mm {pos, strand, mismatches = d(j, s)},
+ * 24 bytes, in Find's order: out[off[i], off[i + 1]) region i's, ascending pos, forward before reverse at
+ * equal pos -- where the two strands may carry different mismatches.  K = 0 gives exactly Find's rows with a
+ * third column of zeros.  Limits: 0 <= K <= SCCG_FIND_MAX_MISMATCHES and K < m; a pattern all of whose
+ * letters may mismatch says nothing and would return every window.
+ *
+ * The host and _device forms, the size query (d_hit == NULL), cap (in hits) / SCCG_E_NOMEM with *n_hit set,
+ * the 8-byte alignment of d_off / d_hit, `stream` and the synchronise before returning are Find's.  Costs:
+ * three kernel launches (two for a size query), one copy of the region list -- the masks and K travel in the
+ * kernel arguments -- and one host read (the total) per call.  The scratch, 2 bits and two 4-bit distances
+ * per candidate start (34 + 128 words of 8 bytes per 960 candidates, 1.35 bytes a candidate), lives in the
+ * staging the call grows; sccg_reader_device_bytes does not change.
+ *
+ * SCCG_E_INVALID, nothing written, sccg_last_error naming the first offender, in this order: NULL handles,
+ * out or n_hit (no message); the pattern, as Find; unknown flag bits; max_mismatches >
+ * SCCG_FIND_MAX_MISMATCHES or >= m (the message holds the word "mismatches" and the number); alignment;
+ * the regions, exactly as Find. */
+#define SCCG_FIND_MAX_MISMATCHES 15
+typedef struct { int64_t pos, strand, mismatches; } sccg_hit_mm;   /* strand 0 forward, 1 reverse */
+int sccg_reader_find_approx(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions, size_t n, uint32_t flags,
+                            uint32_t max_mismatches, int64_t* off /*host, n + 1; may be NULL*/, sccg_buf* out /*sccg_hit_mm[]*/);
+int sccg_reader_find_approx_device(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions /*host*/, size_t n,
+                                   uint32_t flags, uint32_t max_mismatches, void* d_off /*int64[n + 1] or NULL*/, void* d_hit,
+                                   size_t cap /*hits*/, size_t* n_hit, void* stream);
+int sccg_cohort_find_approx(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n,
+                            uint32_t flags, uint32_t max_mismatches, int64_t* off, sccg_buf* out);
+int sccg_cohort_find_approx_device(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions /*host*/,
+                                   size_t n, uint32_t flags, uint32_t max_mismatches, void* d_off, void* d_hit, size_t cap,
+                                   size_t* n_hit, void* stream);
 
 void sccg_buf_free(sccg_buf* b);
 

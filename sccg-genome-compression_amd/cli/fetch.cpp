@@ -15,7 +15,8 @@
 // N runs.  --origin together with -i is a usage error.
 // `fetch --locate ...` and `fetch --lift ...` (first argument only) ask the other way round, from the
 // reference to the sequence: locate_main and lift_main below.
-// `fetch --find <PATTERN> ...` (first argument only) asks where an IUPAC pattern occurs: find_main below.
+// `fetch --find <PATTERN> ...` (first argument only) asks where an IUPAC pattern occurs: find_main below;
+// `fetch --find-approx <K> <PATTERN> ...` where it occurs within K substitutions: find_approx_main.
 #include "cli_common.h"
 
 #include <cstring>
@@ -264,7 +265,109 @@ static int find_main(int argc, char* argv[]) {
     return 0;
 }
 
+// `fetch --find-approx <K> <PATTERN> <record_file> <reference_file> <region>...`: find_main with up to K
+// substitutions (sccg_reader_find_approx): per region `>begin-end`, then `pos strand mismatches bases` per hit.
+// K is decimal, at most SCCG_FIND_MAX_MISMATCHES and less than the pattern's length; a malformed K, pattern or
+// region is a usage error before the GPU is touched.
+static int find_approx_main(int argc, char* argv[]) {
+    const std::string ks = argc > 2 ? argv[2] : "", pat = argc > 3 ? argv[3] : "";
+    const auto is_flag = [](const std::string& a) {
+        return a == "-i" || a == "--reverse-complement" || a == "--origin" || a == "--locate" || a == "--lift" || a == "--find" ||
+               a == "--find-approx";
+    };
+    const bool mixed = is_flag(ks) || is_flag(pat);
+    std::string err;
+    int64_t K = 0;
+    std::vector<sccg_region> regions;
+    if (argc >= 7 && !mixed) {
+        if (sccg_find_pattern_masks(pat.data(), pat.size(), nullptr, nullptr) != SCCG_OK)
+            err = "malformed pattern '" + pat + "' (1 to " + std::to_string(SCCG_FIND_MAX_PATTERN) +
+                  " IUPAC nucleotide letters, ACGTURYSWKMBDHVN in either case)";
+        else if (!parse_pos(ks, &K) || K > SCCG_FIND_MAX_MISMATCHES || K >= (int64_t)pat.size())
+            err = "malformed mismatches '" + ks + "' (decimal, 0 to " + std::to_string(SCCG_FIND_MAX_MISMATCHES) +
+                  " and less than the pattern's " + std::to_string(pat.size()) + " letters)";
+        for (int i = 6; i < argc && err.empty(); i++) {
+            const std::string a = argv[i];
+            const size_t dash = a.find('-');
+            int64_t b = 0, e = 0;
+            const bool ok = dash == std::string::npos ? parse_pos(a, &b) && (e = b, true)
+                                                      : parse_pos(a.substr(0, dash), &b) && parse_pos(a.substr(dash + 1), &e);
+            if (!ok || b < 1 || e < b) err = "malformed region '" + a + "' (begin-end, 1-based, inclusive, begin <= end)";
+            regions.push_back(sccg_region{b - 1, e});
+        }
+    }
+    if (argc < 7 || mixed || !err.empty()) {
+        if (!err.empty()) std::cerr << "Error: " << err << "\n";
+        std::cerr << "Usage: " << argv[0] << " --find-approx <K> <PATTERN> <record_file> <reference_file> <region>...\n"
+                  << "  K: substitutions allowed, 0 to " << SCCG_FIND_MAX_MISMATCHES << " and less than the pattern's length\n"
+                  << "  PATTERN: 1 to " << SCCG_FIND_MAX_PATTERN << " IUPAC nucleotide letters (N: any of A, C, G, T); both strands are searched;\n"
+                  << "      a sequence base that is not A, C, G or T is a mismatch against every letter\n"
+                  << "  region: begin-end (1-based, inclusive) or pos; prints >begin-end, then one line per hit:\n"
+                  << "      pos strand(+|-) mismatches bases -- the window's leftmost position and its bases on the forward strand\n"
+                  << "  --find-approx is the first argument only, not with -i, --origin, --locate, --lift or --find\n";
+        return 1;
+    }
+    std::string ref, rec;
+    if (!slurp(argv[5], ref)) {
+        std::cerr << "Greska pri otvaranju reference: " << argv[5] << "\n";
+        return 1;
+    }
+    if (!slurp(argv[4], rec)) {
+        std::cerr << "Greska pri otvaranju datoteke: " << argv[4] << "\n";
+        return 1;
+    }
+    sccg_ctx* ctx = nullptr;
+    int rc = sccg_ctx_create(cli_device(), &ctx);
+    if (rc) {
+        std::cerr << "Error: no usable GPU (sccg_ctx_create rc=" << rc << ")\n";
+        return 1;
+    }
+    sccg_reader* rd = nullptr;
+    rc = sccg_reader_open(ctx, ref.data(), ref.size(), rec.data(), rec.size(), &rd);
+    if (rc) {
+        std::cerr << "Error opening the record: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    sccg_buf hits{}, bases{};
+    std::vector<int64_t> off(regions.size() + 1);
+    std::vector<sccg_hit_mm> hit;
+    rc = sccg_reader_find_approx(rd, pat.data(), pat.size(), regions.data(), regions.size(), SCCG_FIND_FWD | SCCG_FIND_REV, (uint32_t)K,
+                                 off.data(), &hits);
+    if (!rc) {   // the windows of all hits in one fetch
+        hit.resize(hits.len / sizeof(sccg_hit_mm));
+        if (!hit.empty()) memcpy(hit.data(), hits.data, hit.size() * sizeof(sccg_hit_mm));
+        std::vector<sccg_region> win(hit.size());
+        for (size_t k = 0; k < hit.size(); k++) win[k] = sccg_region{hit[k].pos, hit[k].pos + (int64_t)pat.size()};
+        rc = sccg_reader_fetch(rd, win.data(), win.size(), 0, &bases);
+    }
+    if (rc) {
+        std::cerr << "Error finding: " << sccg_last_error(ctx) << " (rc=" << rc << ")\n";
+        sccg_buf_free(&hits);
+        sccg_reader_close(rd);
+        sccg_ctx_destroy(ctx);
+        return 1;
+    }
+    std::string out;
+    for (size_t i = 0; i < regions.size(); i++) {
+        out += ">" + std::to_string(regions[i].begin + 1) + "-" + std::to_string(regions[i].end) + "\n";
+        for (int64_t k = off[i]; k < off[i + 1]; k++) {
+            const sccg_hit_mm& h = hit[(size_t)k];
+            out += std::to_string(h.pos + 1) + "\t" + (h.strand ? "-" : "+") + "\t" + std::to_string(h.mismatches) + "\t";
+            out.append(bases.data + (size_t)k * pat.size(), pat.size());
+            out += '\n';
+        }
+    }
+    std::cout << out;
+    sccg_buf_free(&hits);
+    sccg_buf_free(&bases);
+    sccg_reader_close(rd);
+    sccg_ctx_destroy(ctx);
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
+    if (argc > 1 && std::string(argv[1]) == "--find-approx") return find_approx_main(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "--find") return find_main(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "--lift") return lift_main(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "--locate") return locate_main(argc, argv);

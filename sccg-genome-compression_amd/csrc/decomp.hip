@@ -1678,6 +1678,157 @@ __global__ __launch_bounds__(SCCG_BLOCK) void k_find_write(const FindArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Find with mismatches (sccg_*_find_approx*): the hits within K <= SCCG_FIND_MAX_MISMATCHES substitutions.
+// Find's geometry, front and scan with another match and a third column; the exact kernels above are
+// left as they are, so what sccg_*_find* launches does not change.
+//   match   nib_any(x & mask) has bit 0 of a nibble for every letter that matches and is a subset of
+//           lm (a letter's mask is never zero), so the letters that do not are lm ^ that word and a
+//           start's distance is its population count summed over the pattern's words: two v_bcnt a word
+//           and strand where the exact kernel compares, no branch.  A base of code 4 packs as nibble 0
+//           and so mismatches every letter, N included.  So do the zero nibbles beyond a span's window
+//           [j0, je), but no start the gate `r < cnt` lets through sees them: a lane's cnt starts are
+//           starts of the span, j < j1, and their last letter is at j + m - 1 <= j1 + m - 2 = je - 1.
+//   k_find_mm_count  leaves Find's hit word per lane and, beside it, two 64-bit words of 4-bit
+//           distances, one per strand, nibble r for the lane's flat slot r; a nibble is the distance
+//           where the hit bit is set (d <= K <= 15) and 0 elsewhere.  All three are kept in registers
+//           across the tile's spans and stored once.  Scratch: 34 + 128 words of 8 bytes a tile of 960
+//           candidates, 1.35 bytes a candidate.
+//   k_find_mm_write  k_find_write's walk over the hit word -- no decode -- storing {pos, strand, d};
+//           the regions' offsets come from the hit words exactly as there.
+// LDS per block: k_find_count's 6,912 bytes.  Every loop is bounded by a data size or a constant; no
+// wave waits for another; plain vector stores.
+// ---------------------------------------------------------------------------------------------
+struct FindMmArgs {
+    FindArgs B;        // Find's arguments; B.hit is not used
+    uint32_t K;        // mismatches allowed, <= SCCG_FIND_MAX_MISMATCHES
+    uint64_t* dist;    // W * 64 * 2: a lane's distances, forward then reverse
+    sccg_hit_mm* hit;
+};
+static_assert(SCCG_FIND_MAX_MISMATCHES <= 15, "a distance is one nibble");
+
+template <bool COHORT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_find_mm_count(const FindMmArgs M) {
+    __shared__ uint8_t tile[WPB][FT_W];
+    __shared__ uint64_t pack[WPB][FD_WORDS];
+    __shared__ uint8_t stg[WPB][2 * TK_B];
+    const FindArgs& A = M.B;
+    const int64_t w = (int64_t)blockIdx.x * WPB + wave_in_block();
+    if (w >= A.W) return;
+    const int lane = lane_id();
+    uint8_t* sdec = tile[wave_in_block()];
+    uint64_t* pk = pack[wave_in_block()];
+    uint8_t* st = stg[wave_in_block()];
+    const FetchTile T = find_tile(A, w);
+    if (lane < FD_WORDS - 64) pk[64 + lane] = 0;   // (read by the last lanes' starts beyond cnt only)
+    uint32_t bits = 0;
+    uint64_t df = 0, dr = 0;
+    if (T.w0 < T.fend)
+        fetch_spans<COHORT>(A.F, T, [&](const DcCohortEntry& E, int64_t j0, int64_t j1, bool, int64_t j, int k0, int k1) {
+            const int64_t je = j1 + (A.m - 1);   // <= the region's end: j1 - 1 is a candidate
+            const FetchSpan sp = fetch_decode_span(E.S, j0, je, sdec, st);
+            int64_t q = j0 + (int64_t)lane * 16;
+            uint64_t word = 0;
+            if (q < je) {
+                NCursor N(E, sp.rn0);
+                const int cnt = je - q < 16 ? (int)(je - q) : 16;
+                for (int t = 0; t < cnt; t++) {
+                    N.seek(q);
+                    const uint32_t c = q >= N.s ? 4u : base_code(sdec[q - N.b - sp.d0]);
+                    if (c < 4u) word |= (uint64_t)(1u << c) << (4 * t);
+                    q++;
+                }
+            }
+            pk[lane] = word;
+            wave_sync();
+            if (k0 < k1) {
+                const int s0 = (int)(j - j0), a = s0 >> 4, sh = s0 & 15, cnt = k1 - k0;
+                uint64_t raw[6], v[5];
+#pragma unroll
+                for (int k = 0; k < 6; k++) raw[k] = pk[a + k];
+#pragma unroll
+                for (int k = 0; k < 5; k++) v[k] = nib_shr(raw[k], raw[k + 1], sh);
+                uint32_t hf = 0, hr = 0;
+                uint64_t nf = 0, nr = 0;
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    uint32_t f = 0, rv = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (k < A.nw) {
+                            const uint64_t x = nib_shr(v[k], v[k + 1], r);
+                            f += (uint32_t)__popcll(A.lm[k] ^ nib_any(x & A.pf[k]));
+                            rv += (uint32_t)__popcll(A.lm[k] ^ nib_any(x & A.pr[k]));
+                        }
+                    const bool isf = A.fwd != 0 && f <= M.K && r < cnt, isr = A.rev != 0 && rv <= M.K && r < cnt;
+                    hf |= (uint32_t)isf << r;
+                    hr |= (uint32_t)isr << r;
+                    nf |= (uint64_t)(isf ? f : 0u) << (4 * r);
+                    nr |= (uint64_t)(isr ? rv : 0u) << (4 * r);
+                }
+                // slot k0 + r: the nibbles shifted out are those of r >= 16 - k0 >= cnt, all zero
+                bits |= (hf << k0) | (hr << (16 + k0));
+                df |= nf << (4 * k0);
+                dr |= nr << (4 * k0);
+            }
+        });
+    A.bits[w * 64 + lane] = bits;
+    reinterpret_cast<ulonglong2*>(M.dist)[w * 64 + lane] = make_ulonglong2(df, dr);
+    const int64_t total = wave_sum((int64_t)__popc(bits));
+    if (lane == 0) A.wcnt[w] = total;
+}
+
+template <bool COHORT>
+__global__ __launch_bounds__(SCCG_BLOCK) void k_find_mm_write(const FindMmArgs M) {
+    const FindArgs& A = M.B;
+    // the regions' offsets: the hits before flat position pre[i]
+    if (A.off) {
+        const int64_t total = A.woff[A.W];
+        for (int64_t i = (int64_t)blockIdx.x * SCCG_BLOCK + threadIdx.x; i <= A.F.nreg; i += (int64_t)gridDim.x * SCCG_BLOCK) {
+            const int64_t f = A.F.pre[i];
+            int64_t o = total;
+            if (f < A.F.F) {
+                const int64_t w = f / FD_TILE;
+                const int sl = (int)(f - w * FD_TILE);
+                const uint32_t* __restrict__ b = A.bits + w * 64;
+                o = A.woff[w];
+                for (int l = 0; l < (sl >> 4); l++) o += __popc(b[l]);
+                const uint32_t low = (1u << (sl & 15)) - 1u;
+                o += __popc(b[sl >> 4] & (low | (low << 16)));
+            }
+            A.off[i] = o;
+        }
+    }
+    const int64_t w = (int64_t)blockIdx.x * WPB + wave_in_block();
+    if (w >= A.W) return;
+    const FetchTile T = find_tile(A, w);
+    if (T.w0 >= T.fend) return;
+    const uint32_t bits = A.bits[w * 64 + lane_id()];
+    const uint32_t c = (uint32_t)__popc(bits);
+    int64_t o = A.woff[w] + (wave_incl_add_dpp(c) - c);   // the lane's first row
+    if (!__ballot(c != 0)) return;
+    const ulonglong2 d = reinterpret_cast<const ulonglong2*>(M.dist)[w * 64 + lane_id()];
+    sccg_hit_mm* __restrict__ hit = M.hit;
+    const int64_t cap = A.cap;
+    fetch_spans<COHORT>(A.F, T, [&](const DcCohortEntry&, int64_t, int64_t, bool, int64_t j, int k0, int k1) {
+        if (k0 >= k1) return;
+        uint32_t mk = (bits | (bits >> 16)) & ((1u << k1) - (1u << k0));   // the span's slots with a hit
+        while (mk) {
+            const int k = __ffs((int)mk) - 1;
+            mk &= mk - 1;
+            const int64_t pos = j + (k - k0);
+            if ((bits >> k) & 1u) {
+                if (o < cap) hit[o] = sccg_hit_mm{pos, 0, (int64_t)((d.x >> (4 * k)) & 15u)};
+                o++;
+            }
+            if ((bits >> (16 + k)) & 1u) {
+                if (o < cap) hit[o] = sccg_hit_mm{pos, 1, (int64_t)((d.y >> (4 * k)) & 15u)};
+                o++;
+            }
+        }
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
 // The R' -> R map of a shared reference: the maximal runs of the byte 'N' (uppercase only: a
 // lowercase 'n' survives into R' as "N", decompression.cpp:108 before :110) in the stripped,
 // original-case reference R.  A block takes RM_TILE bytes, a thread 16 of them in one load; a run
@@ -2056,6 +2207,40 @@ int fd_write(const FdCall& c, int64_t cap, int64_t* d_off, sccg_hit* d_hit, hipS
     A.cap = cap;
     void (*const kernel)(FindArgs) = c.src ? k_find_write<false> : k_find_write<true>;
     PROF_LAUNCH(PROF_FETCH, s, kernel, dim3((unsigned)((A.W + WPB - 1) / WPB)), dim3(SCCG_BLOCK), 0, s, A);
+    SCCG_HIP(hipGetLastError());
+    return 0;
+}
+
+namespace {
+// scratch: Find's 34 W + 1 words, then the W * 64 pairs of distance words on a 16-byte boundary
+FindMmArgs fa_args(const FdCall& c) {
+    FindMmArgs M{};
+    M.B = fd_args(c);
+    M.K = (uint32_t)c.K;
+    M.dist = reinterpret_cast<uint64_t*>(((uintptr_t)(M.B.woff + M.B.W + 1) + 15) & ~(uintptr_t)15);
+    return M;
+}
+}  // namespace
+
+int64_t fa_scratch_words(int64_t F) { return fd_scratch_words(F) + 128 * fd_tiles(F) + 1; }
+
+int fa_count(const FdCall& c, hipStream_t s) {
+    if (c.nreg <= 0 || c.m < 1 || c.m > FD_MAXM || c.F < 0 || c.K < 0 || c.K > SCCG_FIND_MAX_MISMATCHES) return SCCG_E_INVALID;
+    const FindMmArgs M = fa_args(c);
+    void (*const kernel)(FindMmArgs) = c.src ? k_find_mm_count<false> : k_find_mm_count<true>;
+    PROF_LAUNCH(PROF_FETCH, s, kernel, dim3((unsigned)((M.B.W + WPB - 1) / WPB)), dim3(SCCG_BLOCK), 0, s, M);
+    SCCG_HIP(hipGetLastError());
+    return sg_scan(M.B.wcnt, M.B.woff, M.B.W, s);
+}
+
+int fa_write(const FdCall& c, int64_t cap, int64_t* d_off, sccg_hit_mm* d_hit, hipStream_t s) {
+    if (c.nreg <= 0 || c.m < 1 || c.m > FD_MAXM || c.F < 0 || cap < 0) return SCCG_E_INVALID;
+    FindMmArgs M = fa_args(c);
+    M.B.off = d_off;
+    M.B.cap = cap;
+    M.hit = d_hit;
+    void (*const kernel)(FindMmArgs) = c.src ? k_find_mm_write<false> : k_find_mm_write<true>;
+    PROF_LAUNCH(PROF_FETCH, s, kernel, dim3((unsigned)((M.B.W + WPB - 1) / WPB)), dim3(SCCG_BLOCK), 0, s, M);
     SCCG_HIP(hipGetLastError());
     return 0;
 }

@@ -25,9 +25,17 @@ struct FdCall {
     uint8_t fwd[SCCG_FIND_MAX_PATTERN], rev[SCCG_FIND_MAX_PATTERN];
     bool want_fwd, want_rev;
     int64_t* d_scratch;
+    int K;   // find with mismatches only: substitutions allowed, 0 <= K <= SCCG_FIND_MAX_MISMATCHES, K < m
 };
 int64_t fd_candidates(int64_t len, int m);
 int64_t fd_scratch_words(int64_t F);
 const int64_t* fd_total_slot(const FdCall& c);
 int fd_count(const FdCall& c, hipStream_t s);
 int fd_write(const FdCall& c, int64_t cap, int64_t* d_off, sccg_hit* d_hit, hipStream_t s);
+
+// Find with mismatches: the same call, c.K set, the same three launches over the same flat space and the same
+// total slot; a hit is a start within K substitutions on a strand, a row {pos, strand, mismatches}.  The
+// scratch is fa_scratch_words(F) int64: Find's 34 a tile and 128 a tile of 4-bit distances.
+int64_t fa_scratch_words(int64_t F);
+int fa_count(const FdCall& c, hipStream_t s);
+int fa_write(const FdCall& c, int64_t cap, int64_t* d_off, sccg_hit_mm* d_hit, hipStream_t s);

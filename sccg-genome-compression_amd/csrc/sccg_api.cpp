@@ -2324,6 +2324,17 @@ int find_pattern_check(sccg_ctx* ctx, const char* pattern, size_t m, uint32_t fl
     return SCCG_OK;
 }
 
+// the same for a find with mismatches, K behind the flags: at most SCCG_FIND_MAX_MISMATCHES and fewer than the letters
+int find_approx_check(sccg_ctx* ctx, const char* pattern, size_t m, uint32_t flags, uint32_t K, FdCall* c) {
+    const int rc = find_pattern_check(ctx, pattern, m, flags, c);
+    if (rc) return rc;
+    if (K > SCCG_FIND_MAX_MISMATCHES || K >= m)
+        return ctx->fail(SCCG_E_INVALID, "%u mismatches asked of a pattern of %zu letters: 0 to %d, and fewer than the letters, are searched",
+                         K, m, SCCG_FIND_MAX_MISMATCHES);
+    c->K = (int)K;
+    return SCCG_OK;
+}
+
 // a cohort's regions: one pass, the first offender in list order decides; the strands are the call's
 int cohort_find_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t n) {
     sccg_ctx* ctx = co->ctx;
@@ -2348,10 +2359,24 @@ int cohort_find_check(sccg_cohort* co, const sccg_cohort_region* regions, size_t
 // behind it in the same allocation.  The three forms are segments_run's: d_hit given -- count, scan and write
 // queued back to back (the write is clipped to cap on the device) and the one host read of the total behind them,
 // which is the call's synchronise and its capacity check; d_hit NULL with h_out NULL -- the size query, two launches
-// and the read; h_out -- two launches, the read (it sizes the buffers), the write, one sync.
-template <typename Regions>
+// and the read; h_out -- two launches, the read (it sizes the buffers), the write, one sync.  Ops: the row, the scratch
+// and the launchers of find (FindOps) or of find with mismatches (FindApproxOps).
+struct FindOps {
+    typedef sccg_hit Row;
+    static int64_t scratch_words(int64_t F) { return fd_scratch_words(F); }
+    static int count(const FdCall& c, hipStream_t s) { return fd_count(c, s); }
+    static int write(const FdCall& c, int64_t cap, int64_t* d_off, Row* d_hit, hipStream_t s) { return fd_write(c, cap, d_off, d_hit, s); }
+};
+struct FindApproxOps {   // c.K set
+    typedef sccg_hit_mm Row;
+    static int64_t scratch_words(int64_t F) { return fa_scratch_words(F); }
+    static int count(const FdCall& c, hipStream_t s) { return fa_count(c, s); }
+    static int write(const FdCall& c, int64_t cap, int64_t* d_off, Row* d_hit, hipStream_t s) { return fa_write(c, cap, d_off, d_hit, s); }
+};
+template <typename Ops, typename Regions>
 int find_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, FdCall c, void* d_off, void* d_hit, size_t cap,
              size_t* n_hit, int64_t* h_off, sccg_buf* h_out, hipStream_t s) {
+    typedef typename Ops::Row Row;
     constexpr bool samples = Regions::samples;
     HIPTRY(hipSetDevice(ctx->device));
     int64_t F = 0;
@@ -2361,7 +2386,7 @@ int find_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, Fd
     }
     const size_t n4 = (n * sizeof(int32_t) + 7) & ~(size_t)7;
     const size_t img = (2 * n + 1) * sizeof(int64_t) + (samples ? n4 : 0);
-    const size_t bytes = img + (size_t)fd_scratch_words(F) * sizeof(int64_t);
+    const size_t bytes = img + (size_t)Ops::scratch_words(F) * sizeof(int64_t);
     size_t rcap = 0;
     hipError_t e = st.reserve_regions(bytes, &rcap);
     if (e != hipSuccess) return reader_alloc_fail(ctx, e, rcap);
@@ -2384,10 +2409,10 @@ int find_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, Fd
     c.nreg = (int64_t)n;
     c.F = F;
     c.d_scratch = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(d) + img);
-    TRY(fd_count(c, s));
+    TRY(Ops::count(c, s));
     if (!h_out && d_hit)   // (no host wait before it: slots beyond cap are not written, and such a call fails below)
-        TRY(fd_write(c, (int64_t)(cap < (size_t)INT64_MAX / 64 ? cap : (size_t)INT64_MAX / 64), reinterpret_cast<int64_t*>(d_off),
-                     reinterpret_cast<sccg_hit*>(d_hit), s));
+        TRY(Ops::write(c, (int64_t)(cap < (size_t)INT64_MAX / 64 ? cap : (size_t)INT64_MAX / 64), reinterpret_cast<int64_t*>(d_off),
+                     reinterpret_cast<Row*>(d_hit), s));
     int64_t total = 0;
     {
         const RbItem it{fd_total_slot(c), &total, (int)sizeof total};
@@ -2399,7 +2424,7 @@ int find_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, Fd
         if (d_hit && (size_t)total > cap) return ctx->fail(SCCG_E_NOMEM, "output needs %zu hits", (size_t)total);
         return SCCG_OK;
     }
-    const size_t hit_bytes = (size_t)total * sizeof(sccg_hit), off_bytes = (n + 1) * sizeof(int64_t);
+    const size_t hit_bytes = (size_t)total * sizeof(Row), off_bytes = (n + 1) * sizeof(int64_t);
     char* hb = (char*)malloc(hit_bytes + 1);
     if (!hb) return ctx->fail(SCCG_E_NOMEM, "host allocation failed");
     const auto fill = [&]() -> int {
@@ -2407,7 +2432,7 @@ int find_run(sccg_ctx* ctx, FetchStage& st, const Regions& regions, size_t n, Fd
         e = st.reserve_out(hit_bytes + off_bytes, &ocap);
         if (e != hipSuccess) return reader_alloc_fail(ctx, e, ocap);
         int64_t* o = reinterpret_cast<int64_t*>(st.d_out);   // the offsets, then the hits
-        TRY(fd_write(c, total, o, reinterpret_cast<sccg_hit*>(o + n + 1), s));
+        TRY(Ops::write(c, total, o, reinterpret_cast<Row*>(o + n + 1), s));
         HIPTRY(hipStreamSynchronize(s));
         if (hit_bytes) HIPTRY(hipMemcpy(hb, o + n + 1, hit_bytes, hipMemcpyDeviceToHost));
         if (h_off) HIPTRY(hipMemcpy(h_off, o, off_bytes, hipMemcpyDeviceToHost));
@@ -2964,7 +2989,7 @@ int sccg_reader_find_device(sccg_reader* reader, const char* pattern, size_t m, 
     if (rc) return rc;
     if (!n) return segments_none(ctx, d_hit ? d_off : nullptr, n_hit, nullptr, nullptr, s);
     c.src = &reader->src;
-    return find_run(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, d_off, d_hit, cap, n_hit, nullptr, nullptr, s);
+    return find_run<FindOps>(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, d_off, d_hit, cap, n_hit, nullptr, nullptr, s);
 }
 
 int sccg_reader_find(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions, size_t n, uint32_t flags,
@@ -2978,7 +3003,7 @@ int sccg_reader_find(sccg_reader* reader, const char* pattern, size_t m, const s
     if (rc) return rc;   // (nothing written: *out and off are the caller's as they were)
     if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
     c.src = &reader->src;
-    return find_run(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
+    return find_run<FindOps>(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
 }
 
 int sccg_cohort_find_device(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n,
@@ -2993,7 +3018,7 @@ int sccg_cohort_find_device(sccg_cohort* cohort, const char* pattern, size_t m, 
     if (rc) return rc;
     if (!n) return segments_none(ctx, d_hit ? d_off : nullptr, n_hit, nullptr, nullptr, s);
     c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
-    return find_run(ctx, cohort->stage, CohortRegions{regions}, n, c, d_off, d_hit, cap, n_hit, nullptr, nullptr, s);
+    return find_run<FindOps>(ctx, cohort->stage, CohortRegions{regions}, n, c, d_off, d_hit, cap, n_hit, nullptr, nullptr, s);
 }
 
 int sccg_cohort_find(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n, uint32_t flags,
@@ -3006,7 +3031,70 @@ int sccg_cohort_find(sccg_cohort* cohort, const char* pattern, size_t m, const s
     if (rc) return rc;
     if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
     c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
-    return find_run(ctx, cohort->stage, CohortRegions{regions}, n, c, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
+    return find_run<FindOps>(ctx, cohort->stage, CohortRegions{regions}, n, c, nullptr, nullptr, 0, nullptr, off, out, ctx->stream);
+}
+
+int sccg_reader_find_approx_device(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions, size_t n,
+                                   uint32_t flags, uint32_t max_mismatches, void* d_off, void* d_hit, size_t cap, size_t* n_hit,
+                                   void* stream) {
+    if (!reader || !n_hit) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    FdCall c{};
+    int64_t F = 0;
+    int rc = find_approx_check(ctx, pattern, m, flags, max_mismatches, &c);
+    if (!rc) rc = segments_align_check(ctx, d_off, d_hit, "d_hit");
+    if (!rc) rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_hit ? d_off : nullptr, n_hit, nullptr, nullptr, s);
+    c.src = &reader->src;
+    return find_run<FindApproxOps>(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, d_off, d_hit, cap, n_hit, nullptr,
+                                   nullptr, s);
+}
+
+int sccg_reader_find_approx(sccg_reader* reader, const char* pattern, size_t m, const sccg_region* regions, size_t n, uint32_t flags,
+                            uint32_t max_mismatches, int64_t* off, sccg_buf* out) {
+    if (!reader || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = reader->ctx;
+    FdCall c{};
+    int64_t F = 0;
+    int rc = find_approx_check(ctx, pattern, m, flags, max_mismatches, &c);
+    if (!rc) rc = fetch_check(reader, regions, n, &F);
+    if (rc) return rc;   // (nothing written: *out and off are the caller's as they were)
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    c.src = &reader->src;
+    return find_run<FindApproxOps>(ctx, reader->stage, ReaderRegions{regions, nullptr}, n, c, nullptr, nullptr, 0, nullptr, off, out,
+                                   ctx->stream);
+}
+
+int sccg_cohort_find_approx_device(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n,
+                                   uint32_t flags, uint32_t max_mismatches, void* d_off, void* d_hit, size_t cap, size_t* n_hit,
+                                   void* stream) {
+    if (!cohort || !n_hit) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    FdCall c{};
+    int rc = find_approx_check(ctx, pattern, m, flags, max_mismatches, &c);
+    if (!rc) rc = segments_align_check(ctx, d_off, d_hit, "d_hit");
+    if (!rc) rc = cohort_find_check(cohort, regions, n);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, d_hit ? d_off : nullptr, n_hit, nullptr, nullptr, s);
+    c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
+    return find_run<FindApproxOps>(ctx, cohort->stage, CohortRegions{regions}, n, c, d_off, d_hit, cap, n_hit, nullptr, nullptr, s);
+}
+
+int sccg_cohort_find_approx(sccg_cohort* cohort, const char* pattern, size_t m, const sccg_cohort_region* regions, size_t n,
+                            uint32_t flags, uint32_t max_mismatches, int64_t* off, sccg_buf* out) {
+    if (!cohort || !out) return SCCG_E_INVALID;
+    sccg_ctx* ctx = cohort->ctx;
+    FdCall c{};
+    int rc = find_approx_check(ctx, pattern, m, flags, max_mismatches, &c);
+    if (!rc) rc = cohort_find_check(cohort, regions, n);
+    if (rc) return rc;
+    if (!n) return segments_none(ctx, nullptr, nullptr, off, out, ctx->stream);
+    c.d_tab = reinterpret_cast<const DcCohortEntry*>(cohort->d_tab);
+    return find_run<FindApproxOps>(ctx, cohort->stage, CohortRegions{regions}, n, c, nullptr, nullptr, 0, nullptr, off, out,
+                                   ctx->stream);
 }
 
 // match_sequences seam (compression.cpp:36): local segments or the windowed global walk

@@ -30,6 +30,7 @@ LOCATE_REF_N = -2      # SCCG_LOCATE_REF_N: the position lies in an N run of the
 ORIGIN_LITERAL, ORIGIN_N = -1, -2                          # "origin" values that are no reference position
 FIND_MAX_PATTERN = 64                                      # SCCG_FIND_MAX_PATTERN
 FIND_STRANDS = {"+": 1, "-": 2, "both": 3}                 # SCCG_FIND_FWD, SCCG_FIND_REV, both
+FIND_MAX_MISMATCHES = 15                                   # SCCG_FIND_MAX_MISMATCHES
 ERRORS = {1: "SCCG_E_INVALID", 2: "SCCG_E_HIP", 3: "SCCG_E_NOMEM", 4: "SCCG_E_DELTA_STOI",
           5: "SCCG_E_FORMAT", 6: "SCCG_E_RANGE", 7: "SCCG_E_PARSE", 8: "SCCG_E_UNSUPPORTED",
           9: "SCCG_E_INTERNAL", 10: "SCCG_E_OPEN_REF", 11: "SCCG_E_OPEN_TGT", 12: "SCCG_E_WRITE"}
@@ -224,6 +225,14 @@ def load_library():
         lib.sccg_reader_find_device.argtypes = [vp, c, sz, ctypes.POINTER(Region), sz, u32, vp, vp, sz, ctypes.POINTER(sz), vp]
         lib.sccg_cohort_find.argtypes = [vp, c, sz, ctypes.POINTER(CohortRegion), sz, u32, i64p, ctypes.POINTER(Buf)]
         lib.sccg_cohort_find_device.argtypes = [vp, c, sz, ctypes.POINTER(CohortRegion), sz, u32, vp, vp, sz, ctypes.POINTER(sz), vp]
+    if hasattr(lib, "sccg_reader_find_approx"):   # (absent from builds older than find with mismatches: A/B runs)
+        i64p, u32 = ctypes.POINTER(i64), ctypes.c_uint32
+        lib.sccg_reader_find_approx.argtypes = [vp, c, sz, ctypes.POINTER(Region), sz, u32, u32, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_reader_find_approx_device.argtypes = [vp, c, sz, ctypes.POINTER(Region), sz, u32, u32, vp, vp, sz,
+                                                       ctypes.POINTER(sz), vp]
+        lib.sccg_cohort_find_approx.argtypes = [vp, c, sz, ctypes.POINTER(CohortRegion), sz, u32, u32, i64p, ctypes.POINTER(Buf)]
+        lib.sccg_cohort_find_approx_device.argtypes = [vp, c, sz, ctypes.POINTER(CohortRegion), sz, u32, u32, vp, vp, sz,
+                                                       ctypes.POINTER(sz), vp]
     lib.sccg_profile.argtypes = [vp, ctypes.c_int]
     lib.sccg_profile_mask.argtypes = [vp, ctypes.c_uint32]
     lib.sccg_profile_get.argtypes = [vp, c, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
@@ -753,6 +762,22 @@ class Reader:
         return _segments_tensor(self.ctx, self.lib.sccg_reader_find_device, self.ptr, arr, len(regions), stream, cols=2,
                                 head=(pat, len(pat)), mid=(flags,))
 
+    def find_approx(self, pattern, regions, mismatches, strands="both"):
+        """find() within `mismatches` substitutions (sccg_reader_find_approx; 0 <= mismatches <= FIND_MAX_MISMATCHES,
+        fewer than the pattern's letters): (off int64 [n + 1], hits int64 [h, 3]), rows (pos, strand, mismatches) in
+        find()'s order.  A sequence base that is not A, C, G or T is a mismatch against every letter, N included."""
+        regions, arr = self._regions(regions)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_host(self.ctx, self.lib.sccg_reader_find_approx, self.ptr, arr, len(regions), cols=3,
+                              head=(pat, len(pat)), mid=(flags, _find_mismatches(mismatches)))
+
+    def find_approx_tensor(self, pattern, regions, mismatches, strands="both", stream=None):
+        """find_approx() into torch tensors on the context's device."""
+        regions, arr = self._regions(regions)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_tensor(self.ctx, self.lib.sccg_reader_find_approx_device, self.ptr, arr, len(regions), stream, cols=3,
+                                head=(pat, len(pat)), mid=(flags, _find_mismatches(mismatches)))
+
     def locate_tensor(self, ref_positions, stream=None):
         """locate() into torch tensors on the context's device: (pos int64 [n], copies int32 [n])."""
         import numpy as np
@@ -805,6 +830,14 @@ def _find_args(pattern, strands):
     if strands not in FIND_STRANDS:
         raise ValueError(f'strands is "both", "+" or "-", not {strands!r}')
     return pat, FIND_STRANDS[strands]
+
+
+def _find_mismatches(mismatches):
+    """A find_approx call's mismatch bound as the uint32 the library takes (it checks the range)."""
+    k = int(mismatches)
+    if k < 0 or k > 0xFFFFFFFF:
+        raise ValueError(f"mismatches is 0 to {FIND_MAX_MISMATCHES}, not {mismatches!r}")
+    return k
 
 
 def find_pattern_masks(pattern):
@@ -949,6 +982,20 @@ class Cohort:
         pat, flags = _find_args(pattern, strands)
         return _segments_tensor(self.ctx, self.lib.sccg_cohort_find_device, self.ptr, arr, len(rows), stream, cols=2,
                                 head=(pat, len(pat)), mid=(flags,))
+
+    def find_approx(self, pattern, items, mismatches, strands="both"):
+        """Reader.find_approx over the cohort (sccg_cohort_find_approx): items (sample, begin, end)."""
+        rows, arr = self._items(items)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_host(self.ctx, self.lib.sccg_cohort_find_approx, self.ptr, arr, len(rows), cols=3,
+                              head=(pat, len(pat)), mid=(flags, _find_mismatches(mismatches)))
+
+    def find_approx_tensor(self, pattern, items, mismatches, strands="both", stream=None):
+        """find_approx() into torch tensors on the context's device."""
+        rows, arr = self._items(items)
+        pat, flags = _find_args(pattern, strands)
+        return _segments_tensor(self.ctx, self.lib.sccg_cohort_find_approx_device, self.ptr, arr, len(rows), stream, cols=3,
+                                head=(pat, len(pat)), mid=(flags, _find_mismatches(mismatches)))
 
     @staticmethod
     def _loci(items):

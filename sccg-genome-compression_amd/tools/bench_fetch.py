@@ -41,7 +41,11 @@ positions against locate).  --only-find runs the find leg alone: sccg_reader_fin
 1 x 10 Mb and the whole sequence and sccg_cohort_find_device at 1000 x 1 kb, both strands, for GAATTC, a 20-mer cut
 from the sample and N x 21 + GG, beside what the call replaces -- the index fetch of the same regions, then a
 PyTorch mask-table compare over m shifted slices and nonzero on the same stream -- interleaved call by call; every
-timed result is first checked equal to that baseline's rows.  Every shape's bytes are checked against the target FASTA (an origin r >= 0
+timed result is first checked equal to that baseline's rows.  --only-find-approx runs the find-with-mismatches leg alone:
+sccg_*_find_approx_device at the same shapes for a 20-mer cut from the sample plus NGG at K = 0, 2 and 4, both strands,
+beside the exact find of the same pattern and what the call replaces -- the index fetch, an integer sum of mask misses
+over m shifted slices, `<= K` and nonzero on the same stream -- interleaved call by call and checked the same way.
+Every shape's bytes are checked against the target FASTA (an origin r >= 0
 must name the reference base the target's base is, -2 an N).  Prints one JSON line
 (median, min, max of `calls` calls after `warmup`)."""
 import argparse
@@ -674,6 +678,112 @@ def find_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, r
     return out
 
 
+def find_approx_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, ref_len, d_rec, rec_len, truth, S=8):
+    """The find-approx call for a guide + PAM (a 20-mer cut from the sample, then NGG) at K = 0, 2 and 4, both strands,
+    beside (a) the exact find of the same pattern and (b) what the call replaces -- an index fetch, then an integer
+    sum of mask misses over m shifted slices, `<= K` and nonzero, on the same stream -- interleaved call by call, for
+    one reader at four shapes and the S-sample cohort at 1000 x 1 kb."""
+    s = stream.cuda_stream
+    out = {"samples": S, "same_record": True, "shapes": {}}
+    ref = ctx.open_reference_device(d_ref.data_ptr(), ref_len, stream=s)
+    readers = [ref.open_reader_device(d_rec.data_ptr(), rec_len, s) for _ in range(S)]
+    rd, co = readers[0], sccg.Cohort(readers)
+    L = rd.length
+    rng = random.Random(7)
+    at = next(k for k in (rng.randrange(L - 20) for _ in range(10_000)) if all(c in b"ACGT" for c in truth[k:k + 20].upper()))
+    pat = truth[at:at + 20].decode().upper() + "NGG"
+    out["pattern"] = pat
+    pb, m = pat.encode(), len(pat)
+    fwd, rev = sccg.find_pattern_masks(pat)
+    mk = [torch.tensor(list(x), dtype=torch.uint8, device=dev) for x in (fwd, rev)]
+    shapes = [("1x1Mb", "reader", 1, 1_000_000), ("1000x1kb", "reader", 1000, 1000), ("1000x1kb", "cohort", 1000, 1000),
+              ("1x10Mb", "reader", 1, 10_000_000), ("1xwhole", "reader", 1, L)]
+    for name, who, n, ln in shapes:
+        begins = [rng.randrange(L - ln + 1) for _ in range(n)]
+        samp = [k % S for k in range(n)]
+        rng.shuffle(samp)
+        regions = [(b, b + ln) for b in begins]
+        flat = (sccg.Region * n)(*regions)
+        items = (sccg.CohortRegion * n)(*[(b, b + ln, sm, 0) for b, sm in zip(begins, samp)])
+        citems = [(sm, b, b + ln) for b, sm in zip(begins, samp)]
+        d_beg = torch.tensor(begins, dtype=torch.int64, device=dev)
+        approx = lib.sccg_reader_find_approx_device if who == "reader" else lib.sccg_cohort_find_approx_device
+        exact_find = lib.sccg_reader_find_device if who == "reader" else lib.sccg_cohort_find_device
+        h, regs = (rd.ptr, flat) if who == "reader" else (co.ptr, items)
+        got = ctypes.c_size_t()
+        assert exact_find(h, pb, m, regs, n, 3, None, None, 0, ctypes.byref(got), s) == 0
+        ehits = got.value
+        e_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        e_hit = torch.empty((max(ehits, 1), 2), dtype=torch.int64, device=dev)
+        for K in (0, 2, 4):
+            assert approx(h, pb, m, regs, n, 3, K, None, None, 0, ctypes.byref(got), s) == 0   # the size query, outside the timing
+            hits = got.value
+            d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            d_hit = torch.empty((max(hits, 1), 3), dtype=torch.int64, device=dev)
+            base = [None, None]
+
+            def find_approx():
+                assert approx(h, pb, m, regs, n, 3, K, d_off.data_ptr(), d_hit.data_ptr(), hits, ctypes.byref(got), s) == 0 and got.value == hits
+
+            def find():
+                assert exact_find(h, pb, m, regs, n, 3, e_off.data_ptr(), e_hit.data_ptr(), ehits, ctypes.byref(got), s) == 0
+
+            def fetch_sum():
+                c = rd.fetch_tensor(regions, "index", stream=stream) if who == "reader" else co.fetch_tensor(citems, "index", stream=stream)
+                c = c.view(n, ln)
+                C = ln - m + 1
+                d = torch.zeros((n, C, 2), dtype=torch.uint8, device=dev)
+                for t in range(m):   # 1 where the letter's mask lacks the code's bit; code 4 shifts every mask to 0
+                    w = c[:, t:t + C]
+                    d[:, :, 0] += (torch.bitwise_right_shift(mk[0][t], w) & 1) ^ 1
+                    d[:, :, 1] += (torch.bitwise_right_shift(mk[1][t], w) & 1) ^ 1
+                ok = d <= K
+                at = torch.nonzero(ok)   # (a host wait for the count, as the call's one read): rows (region, start, strand)
+                base[0] = torch.stack([d_beg[at[:, 0]] + at[:, 1], at[:, 2], d[at[:, 0], at[:, 1], at[:, 2]].to(torch.int64)], dim=1)
+                base[1] = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(ok.sum(dim=(1, 2)), 0)])
+
+            fetch_sum()   # every timed result is first checked equal to the baseline's rows
+            find_approx()
+            stream.synchronize()
+            exact = bool(torch.equal(base[0], d_hit[:hits]) and torch.equal(base[1], d_off))
+            calls = {"find_approx": find_approx, "find": find, "fetch_plus_sum": fetch_sum}
+            ev = {k: [] for k in calls}
+            for i in range(a.warmup + a.calls):   # interleaved: every leg once per round
+                for k, leg in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    stream.synchronize()
+                    e0.record(stream)
+                    leg()
+                    e1.record(stream)
+                    stream.synchronize()
+                    if i >= a.warmup:
+                        ev[k].append(e0.elapsed_time(e1))
+            exact = exact and bool(torch.equal(base[0], d_hit[:hits]) and torch.equal(base[1], d_off))
+            if K == 0:
+                exact = exact and hits == ehits and bool(torch.equal(d_hit[:hits, :2], e_hit[:ehits]) and torch.equal(d_off, e_off))
+            ctx.profile(True, families=["fetch"])
+            for _ in range(a.calls):
+                find_approx()
+            kern = ctx.profile_get().get("fetch", (0.0, 0))
+            ctx.profile(False)
+            med = {k: statistics.median(v) for k, v in ev.items()}
+            key = f"{name}/{who}/K{K}"
+            out["shapes"][key] = {
+                "bases": n * ln, "hits": hits, "hit_bytes": 24 * hits + 8 * (n + 1), "index_bytes": n * ln,
+                "event_ms": {k: spread(v) for k, v in ev.items()}, "kernels_ms_per_call": round(kern[0] / a.calls, 4),
+                "launches_per_call": kern[1] / a.calls, "sum_over_find_approx": round(med["fetch_plus_sum"] / med["find_approx"], 2),
+                "find_approx_over_find": round(med["find_approx"] / med["find"], 2), "exact": exact}
+            base[0] = base[1] = None
+            del d_off, d_hit
+            print(f"# find-approx {key}: {out['shapes'][key]}", file=sys.stderr, flush=True)
+        del e_off, e_hit
+    co.close()
+    for r in readers:
+        r.close()
+    ref.close()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", default="hg")
@@ -687,6 +797,7 @@ def main() -> None:
     ap.add_argument("--only-segments", action="store_true", help="the segments section alone")
     ap.add_argument("--only-lift", action="store_true", help="the lift section alone")
     ap.add_argument("--only-find", action="store_true", help="the find section alone")
+    ap.add_argument("--only-find-approx", action="store_true", help="the find-with-mismatches section alone")
     a = ap.parse_args()
     import torch
     import sccg
@@ -723,6 +834,14 @@ def main() -> None:
     code = [4] * 256
     for k, ch in enumerate(b"ACGT"):
         code[ch] = code[ch + 32] = k
+    if a.only_find_approx:
+        out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
+               "find_approx": find_approx_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth)}
+        ctx.close()
+        print(json.dumps(out))
+        if not all(v["exact"] for v in out["find_approx"]["shapes"].values()):
+            raise SystemExit("bench_fetch: find-approx section: the hits are not the rows of the fetch-and-sum baseline")
+        return
     if a.only_find:
         out = {"pair": f"{a.profile}-{a.ref_len}-{a.tgt_len}-{a.seed}", "record_bytes": len(rec_h), "calls": a.calls,
                "find": find_section(a, ctx, lib, torch, sccg, dev, stream, d_ref, len(rfa), d_rec, len(rec_h), truth)}
